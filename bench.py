@@ -11,9 +11,11 @@ gradient all-reduce (RCCL) -> SGD step.  Workload at N=1 = BASELINE configs[1] (
 ~1000 proposals per image).  The timed loop cycles through --images (default 8) DISTINCT synthetic images per rank:
 800 ... 1200 proposals (mean 1000), three of the training scales of configs/resnet50_voc.yaml:34 (688 = the median,
 576, 864), different class sets, pseudo-GT counts and PRM clusters - nothing is cached per image.
-Weak scaling: one image per rank.  Rank 0 prints ONE JSON line (contract in the task statement) with `roofline`,
-`roofline_hbm`, `cpu_baseline` and `extra` (sustained >= 5 s loop, iter_size = 4, per-step host->device upload,
-and for N > 1: all-reduce time and overlap).
+Weak scaling: one image per rank.  Rank 0 prints ONE JSON line (contract in the task statement) with `ms_per_step`,
+`roofline` and `roofline_hbm` (HIP events inside the timed steps).  A plain run sets up, warms up, times --steps steps and
+reports; `--full` adds `cpu_baseline` and the `extra` loops (sustained >= 5 s loop, iter_size = 4, per-step host->device
+upload, the reference's literal loop, the TF32-class line, and for N > 1: all-reduce time and overlap).
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs) before the line is printed.
 """
 import argparse
 import json
@@ -42,9 +44,13 @@ def parse_args():
     ap.add_argument("--images", type=int, default=8, help="distinct synthetic images per rank the loop cycles through")
     ap.add_argument("--fixed-image", action="store_true", help="round-1 workload: ONE image (N = config default) repeated")
     ap.add_argument("--iter-size", type=int, default=1, help="images per optimizer step (tools/train.py --iter_size)")
-    ap.add_argument("--sustained", type=float, default=5.0, help="seconds of the extra sustained loop (0 = skip)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra loops (sustained, iter_size=4, upload)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: the extra loops (sustained, "
+                    "iter_size=4, upload, the reference's literal loop, the TF32-class line; for N > 1 the all-reduce) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy: "
+                    "its losses, and the weights after its update and its gradients at fixed seeded positions (see dump_outputs)")
+    ap.add_argument("--sustained", type=float, default=5.0, help="with --full: seconds of the extra sustained loop (0 = skip)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra loops (sustained, iter_size=4, upload)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-overlap-update", action="store_true", help="A/B aid: the whole SGD update on the step's own stream (round 5)")
     ap.add_argument("--trail-wgs", type=int, default=None, help="A/B aid: workgroups of the side-stream update launch")
     ap.add_argument("--dw-form", type=int, default=None, help="A/B aid: kernel form of MaskFuse's late weight-gradient products "
@@ -59,7 +65,10 @@ def parse_args():
     ap.add_argument("--cpu-sample", type=int, default=0, help="proposals in the CPU sample (0 = all)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for a functional "
                                                        "multi-rank check on a box with fewer GPUs than ranks)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -214,6 +223,7 @@ def run(args):
         # the loop; the model here returns that sum itself, from the loss launch)
         loss = out["total_loss"] if "total_loss" in out else sum(v.sum() for v in out["losses"].values())
         loss.backward()          # gradient all-reduce + NumPy-generator settle happen inside (end-of-backward callbacks)
+        state["losses"] = dict(out["losses"], total_loss=loss)         # what the caller received (--dump-outputs)
         return loss
 
     def step(iter_size=1, upload=False):
@@ -277,6 +287,8 @@ def run(args):
     if world > 1:
         dp.comm_works = []
     elapsed = timed(args.steps, iter_size=args.iter_size)          # ---- THE timed region: exactly --steps steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, state["losses"], model, torch, np)
     if os.environ.get("CIM_BENCH_WINDOWS") == "1" and rank == 0:    # debugging aid: further windows of the same length (is the first one special?)
         timer.enabled = False
         print("window 0: %.3f ms" % (1e3 * elapsed / args.steps), file=sys.stderr)
@@ -289,7 +301,7 @@ def run(args):
     images = world * args.steps * args.iter_size
 
     extra = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         if args.sustained > 0:                                       # same loop for >= --sustained seconds (clocks settle)
             per = elapsed / args.steps
             k = max(args.steps, int(np.ceil(args.sustained / per)))
@@ -359,13 +371,13 @@ def run(args):
                                  retain_graph=False, optimizer_overlap_update=bool(opt.overlap_update),
                                  note="the headline loop's four departures from the reference's literal driver loop (the fourth: "
                                  "cim_amd.optim.SGD.overlap_update - the big weights' update runs on the side stream under the next "
-                                 "backbone forward; same arithmetic, same weights bit for bit); extra.reference_loop measures that loop")
+                                 "backbone forward; same arithmetic, same weights bit for bit); extra.reference_loop (--full) measures that loop")
         line["extra"] = extra
         # what the process group itself reports (a SCALE run is checkable: ranks, backend, every rank's own rate)
         line["dist"] = dict(world_size=dist.get_world_size() if world > 1 else 1, backend=(dist.get_backend() if world > 1 else None),
                             devices=torch.cuda.device_count(),
                             per_rank_images_per_s=[args.steps * args.iter_size / t for t in rank_seconds])
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.config, args.cpu_sample)
         print(json.dumps(line))
     if world > 1:
@@ -635,6 +647,31 @@ def init_for_synthetic(model):
             torch.nn.init.constant_(m.bn2.weight, 0.25)
 
 
+DUMP_SAMPLE = 4096      # --dump-outputs: positions sampled per parameter tensor (all of a smaller one)
+
+
+def dump_outputs(out_dir, losses, model, torch, np):
+    """--dump-outputs: what the last timed step handed its caller, as float32 arrays in out_dir.
+    <loss>.npy: the four losses and total_loss, shape (1,).  weights_sample.npy / grads_sample.npy: every trainable parameter
+    after the step's update and its gradient from that step, at DUMP_SAMPLE positions per tensor (np.random.RandomState(0),
+    drawn tensor by tensor in parameters() order), concatenated.  About 1.7 MB at resnet50_voc."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in losses.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v.detach().float().reshape(-1).cpu().numpy())
+    rs = np.random.RandomState(0)
+    weights, grads = [], []
+    for p in model.parameters():
+        if not p.requires_grad:
+            continue
+        n = p.numel()
+        idx = np.sort(rs.randint(0, n, DUMP_SAMPLE)) if n > DUMP_SAMPLE else np.arange(n)
+        idx = torch.from_numpy(idx).to(p.device)
+        weights.append(p.detach().reshape(-1)[idx].float())
+        grads.append(p.grad.detach().reshape(-1)[idx].float() if p.grad is not None else torch.zeros_like(weights[-1]))
+    np.save(os.path.join(out_dir, "weights_sample.npy"), torch.cat(weights).cpu().numpy())
+    np.save(os.path.join(out_dir, "grads_sample.npy"), torch.cat(grads).cpu().numpy())
+
+
 def pmc_traffic(config):
     """HBM bytes per launch from the committed rocprofv3 --pmc passes (FETCH_SIZE and WRITE_SIZE in separate runs of this
     script, tools/pmc_traffic.py).  Only a profile of THIS workload counts: files are named per config and record the
@@ -799,8 +836,8 @@ def report(args, world, elapsed, images, timer, infos, feat, Cf, cfg, gemm_mod, 
                 dtype_note="fp32 tensors and accumulation everywhere; MaskFuse GEMM products evaluated on a scaled two-term fp16 operand "
                            "split written by the operands' producers (3 MFMA products, dropped term <= 2^-22, one power-of-two scale per "
                            "matrix) - measured deviation of losses / gradients from the reference in tests/test_gpu_tolerance.py "
-                           "(profiles/r6/parity_deviation.json); the TF32-class single-product line: extra.tf32_class",
-                config=dict(workload=workload, parallelism="dp%d" % world, inputs="resident in HBM (extra.with_h2d_upload: "
+                           "(profiles/r6/parity_deviation.json); the TF32-class single-product line: extra.tf32_class (--full)",
+                config=dict(workload=workload, parallelism="dp%d" % world, inputs="resident in HBM (extra.with_h2d_upload, --full: "
                             "uploaded from pinned host memory inside every step)"),
                 roofline=roofline, roofline_hbm=hbm)
 

@@ -396,7 +396,7 @@ def test_bench_two_ranks_launch_path():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     backend = "nccl" if torch.cuda.device_count() >= 2 else "gloo"
     cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--backend", backend, "--steps", "2", "--warmup", "1",
-           "--images", "2", "--no-cpu-baseline", "--sustained", "0"]
+           "--images", "2", "--full", "--no-cpu-baseline", "--sustained", "0"]
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
