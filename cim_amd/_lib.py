@@ -77,9 +77,12 @@ SIGNATURES = {
     "cim_loss_grad_combine": [_P] * 8 + [c_int, c_int, c_int, _P],
     "cim_head_act_fwd": [_P, _P, _P, c_int, c_int, c_int, _P],
     "cim_head_act_bwd": [_P, _P, _P, _P, c_int, c_int, c_int, _P],
+    "cim_detect_ws_bytes": [c_int, c_int],
+    "cim_detect_nms_limit": [_P, c_int, _P, c_int, c_int, c_float, c_float, c_int, _P, _P, _P, _P, _P],
+    "cim_detect_corloc": [_P, c_int, c_int, c_int, _P, _P],
 }
 
-ABI_VERSION = 15         # cim_abi_version() of include/cim_hip.h this binding was written against
+ABI_VERSION = 16         # cim_abi_version() of include/cim_hip.h this binding was written against
 _lib = None
 
 
@@ -109,12 +112,12 @@ def load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing
         fn.argtypes = argtypes
-        fn.restype = c_longlong if name in ("cim_conv1x1_bwd_workspace", "cim_conv3x3_nchw_bwd_workspace", "cim_roi_align_bwd_workspace", "cim_roi_align_bwd_scratch", "cim_mining_lds_bytes", "cim_mining_sync_bytes") else c_int
+        fn.restype = c_longlong if name in ("cim_conv1x1_bwd_workspace", "cim_conv3x3_nchw_bwd_workspace", "cim_roi_align_bwd_workspace", "cim_roi_align_bwd_scratch", "cim_mining_lds_bytes", "cim_mining_sync_bytes", "cim_detect_ws_bytes") else c_int
     _lib = lib
     return lib
 
 
-VALUE_RETURNING = {"cim_maxpool2d_out_size", "cim_conv3x3_dx_parts", "cim_mining_sync_bytes", "cim_conv1x1_bwd_workspace", "cim_conv3x3_nchw_bwd_workspace", "cim_conv3x3_nchw_splits", "cim_gemm_small_splits", "cim_mining_lds_bytes", "cim_bn_act_bwd_chunks", "cim_gemm_pair_splits", "cim_roi_align_bwd_workspace", "cim_roi_align_bwd_scratch"}      # return a count, not a status
+VALUE_RETURNING = {"cim_maxpool2d_out_size", "cim_conv3x3_dx_parts", "cim_mining_sync_bytes", "cim_conv1x1_bwd_workspace", "cim_conv3x3_nchw_bwd_workspace", "cim_conv3x3_nchw_splits", "cim_gemm_small_splits", "cim_mining_lds_bytes", "cim_bn_act_bwd_chunks", "cim_gemm_pair_splits", "cim_roi_align_bwd_workspace", "cim_roi_align_bwd_scratch", "cim_detect_ws_bytes"}      # return a count, not a status
 
 
 # split counts / workspace sizes of the body's layers: pure functions of their integer arguments (their tuning switches are read

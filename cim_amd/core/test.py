@@ -16,10 +16,11 @@ Results are device tensors (scores [N, C+... see below]); `.cpu().numpy()` gives
 import numpy as np
 import torch
 
+from .. import detect
 from ..utils import blob as blob_utils
 from .config import cfg
 
-_TEST_DEFAULTS = dict(SCALE=600, MAX_SIZE=1000)                      # lib/core/config.py:123-126
+_TEST_DEFAULTS = dict(SCALE=600, MAX_SIZE=1000, NMS=0.3, DETECTIONS_PER_IM=100, SCORE_THRESH=1e-5)   # lib/core/config.py:123-145
 _AUG_DEFAULTS = dict(ENABLED=False, SCORE_HEUR="AVG", COORD_HEUR="ID", H_FLIP=False, SCALES=(), MAX_SIZE=4000,
                      SCALE_H_FLIP=False, SCALE_SIZE_DEP=False, ASPECT_RATIOS=(), ASPECT_RATIO_H_FLIP=False)   # :167-201
 
@@ -169,3 +170,65 @@ def im_detect_all(model, im, box_proposals=None, masks=None, mat=None, timers=No
         scores, boxes, _, _ = im_detect_bbox(model, im, _test_cfg("SCALE"), _test_cfg("MAX_SIZE"), box_proposals, masks, mat,
                                              path=path, flag=flag, labels=labels)
     return {"scores": scores, "boxes": boxes}
+
+
+# ---------------------------------------------------------------- detections from scores (test.py:320-420) on the device
+def _post_cfg(c, key):
+    t = c.TEST if "TEST" in c else {}
+    return t[key] if key in t else _TEST_DEFAULTS[key]
+
+
+def _post_check(c):
+    t = c.TEST if "TEST" in c else {}
+    for k in ("SOFT_NMS", "BBOX_VOTE"):                                  # config.py:150-165: both off by default
+        if k in t and "ENABLED" in t[k] and t[k]["ENABLED"]:
+            raise NotImplementedError("TEST.%s.ENABLED (no shipped config enables it)" % k)
+
+
+def _nms_limit_records(c, scores, boxes, max_det):
+    """The reference's per-class threshold + NMS + limit of cfg `c`, on the device: host (idx, cls, score, count, boxes)."""
+    _post_check(c)
+    num_classes = c.MODEL.NUM_CLASSES
+    s, b, boxes_h = detect.device_inputs(scores, boxes)
+    det = detect.nms_limit(s, b, _post_cfg(c, "SCORE_THRESH"), _post_cfg(c, "NMS"), max_det, num_classes=num_classes)
+    return detect.to_host(det) + (boxes_h,)
+
+
+def _per_class(values, count):
+    """Records in class order -> one array per class (lengths `count`)."""
+    return np.split(values, np.cumsum(count)[:-1])
+
+
+def _shift(per_class):
+    """test.py:405-409: cls_boxes[0] = [] and class j at j + 1."""
+    return [[]] + list(per_class)
+
+
+def _flat(cls_boxes, num_classes):
+    """test.py:415-418 - np.vstack over j in range(1, num_classes): the LAST class is not in the flat arrays."""
+    im_results = np.vstack([cls_boxes[j] for j in range(1, num_classes)])
+    return im_results[:, -1], im_results[:, :-1]
+
+
+def _dets(boxes_h, idx, score):
+    return np.hstack((boxes_h[idx], score[:, None])).astype(np.float32, copy=False)
+
+
+def box_results_with_nms_and_limit(scores, boxes):
+    """test.py:355-420: (scores, boxes, cls_boxes) with cls_boxes of length NUM_CLASSES + 1, cls_boxes[0] == [] and
+    float32 [k, 5] arrays (x1, y1, x2, y2, score) in ascending proposal order.  scores [N, C] f32 and boxes [N, 4]: device
+    tensors (im_detect_all's) or NumPy arrays."""
+    idx, cls, sc, count, boxes_h = _nms_limit_records(cfg, scores, boxes, _post_cfg(cfg, "DETECTIONS_PER_IM"))
+    cls_boxes = _shift(_per_class(_dets(boxes_h, idx, sc), count))
+    out_scores, out_boxes = _flat(cls_boxes, cfg.MODEL.NUM_CLASSES)
+    return out_scores, out_boxes, cls_boxes
+
+
+def box_results_for_corloc(scores, boxes):
+    """test.py:320-352: per class the highest-scoring proposal (np.argmax), same structures as above (one row a class)."""
+    num_classes = cfg.MODEL.NUM_CLASSES
+    s, _, boxes_h = detect.device_inputs(scores, boxes, boxes_on_device=False)
+    idx, sc = detect.corloc_host(s, num_classes)
+    cls_boxes = _shift(_dets(boxes_h, idx[j:j + 1], sc[j:j + 1]) for j in range(num_classes))
+    out_scores, out_boxes = _flat(cls_boxes, num_classes)
+    return out_scores, out_boxes, cls_boxes

@@ -206,6 +206,33 @@ long long cim_mining_lds_bytes(int N, int K);
 long long cim_mining_sync_bytes(void);
 int cim_mining_step(const cim_mining_args* args, void* sync, void* stream);
 
+/* ------------------------------------------------------------------ detection post-processing (inference's last stage)
+ * Replaces box_results_with_nms_and_limit / box_results_for_corloc (lib/core/test.py:320-420) and
+ * mask_results_with_nms_and_limit{,_get_index} (lib/utils/mask_eval_utils.py:6-108): per class, the proposals with
+ * scores[p, c] > score_thr, greedy box NMS at nms_thr (lib/utils/cython_nms.pyx:36-87), then the per-image limit over ALL
+ * classes: when more than max_det boxes are kept (max_det > 0), only those whose score is >= the max_det-th largest kept
+ * score stay (ties at that score all stay, so more than max_det can remain).
+ *
+ * scores [N, ld] f32 (row p, column c; ld >= C), boxes [N, 4] f32 (x1, y1, x2, y2; 16-byte aligned),
+ * 1 <= N <= CIM_DETECT_MAX_N, C >= 1; other shapes are refused before any launch (-1).  ws: cim_detect_ws_bytes(N, C)
+ * bytes, 8-byte aligned, no initial content.  Outputs:
+ *   det [C * N][3] i32   records (proposal, class, score bit pattern) in (class ascending, proposal ascending) order -
+ *                        what the reference's keep lists hold (keep comes back in ascending proposal order, not by score);
+ *                        the first *total are written
+ *   count_per_class [C]  records per class;  total [1]: records in all
+ * Exactness: the overlap is the pyx's fp32 arithmetic operation for operation (no contraction, correctly rounded
+ * division, its >= / <= ternaries for max / min), compared as ovr >= nms_thr; scores compare as s > score_thr in fp32.
+ * Tie rule: candidates of equal score are visited HIGHER proposal index first (np.argsort(s, kind="stable")[::-1]; the
+ * reference's unstable default sort leaves this order undefined).
+ * Three launches (overlap matrix, one workgroup per class, one limit workgroup); no host synchronisation. */
+#define CIM_DETECT_MAX_N 8192
+long long cim_detect_ws_bytes(int N, int C);
+int cim_detect_nms_limit(const float* scores, int ld, const float* boxes, int N, int C, float score_thr, float nms_thr,
+                         int max_det, void* ws, int32_t* det, int32_t* count_per_class, int32_t* total, void* stream);
+/* CorLoc (lib/core/test.py:320-352): per class, np.argmax(scores[:, c]) - the first index of the maximum, the first NaN if
+ * any.  out [C][2] i32 = (proposal, score bit pattern).  Same shape limits as above. */
+int cim_detect_corloc(const float* scores, int ld, int N, int C, int32_t* out, void* stream);
+
 /* ------------------------------------------------------------------ network-input image (f-3: the data side of the step)
  * Replaces prep_im_for_blob(flag="ToTensor"), lib/utils/blob.py:93-147, called from lib/roi_data/minibatch.py:109-150
  * (training) and lib/core/test.py:464-473 via get_image_blob (inference):
