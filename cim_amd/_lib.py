@@ -80,6 +80,20 @@ SIGNATURES = {
     "cim_detect_ws_bytes": [c_int, c_int],
     "cim_detect_nms_limit": [_P, c_int, _P, c_int, c_int, c_float, c_float, c_int, _P, _P, _P, _P, _P],
     "cim_detect_corloc": [_P, c_int, c_int, c_int, _P, _P],
+    "cim_segm_words": [c_int, c_int],
+    "cim_segm_pack": [_P, _P, c_longlong, c_int, c_int, c_int, _P, _P],
+    "cim_segm_area": [_P, c_int, c_int, _P, _P],
+    "cim_segm_rle_count": [_P, c_int, c_int, c_int, _P, _P],
+    "cim_segm_rle_write": [_P, c_int, c_int, c_int, _P, _P, _P, _P],
+    "cim_segm_rle_decode_ws_bytes": [c_longlong],
+    "cim_segm_rle_decode": [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P],
+    "cim_segm_image_ws_bytes": [c_int, c_int, c_longlong],
+    "cim_segm_record_bytes": [c_int, c_int, c_int, c_int],
+    "cim_segm_eval_image": [_P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_longlong, _P, _P, _P, c_int, _P, c_int,
+                            _P, _P, _P],
+    "cim_segm_accumulate_ws_bytes": [c_longlong, c_int, c_int, c_int],
+    "cim_segm_accumulate": [_P, c_int, c_longlong, c_int, _P, _P, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P,
+                            _P],
 }
 
 ABI_VERSION = 16         # cim_abi_version() of include/cim_hip.h this binding was written against
@@ -112,12 +126,13 @@ def load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing
         fn.argtypes = argtypes
-        fn.restype = c_longlong if name in ("cim_conv1x1_bwd_workspace", "cim_conv3x3_nchw_bwd_workspace", "cim_roi_align_bwd_workspace", "cim_roi_align_bwd_scratch", "cim_mining_lds_bytes", "cim_mining_sync_bytes", "cim_detect_ws_bytes") else c_int
+        fn.restype = c_longlong if name in ("cim_conv1x1_bwd_workspace", "cim_conv3x3_nchw_bwd_workspace", "cim_roi_align_bwd_workspace", "cim_roi_align_bwd_scratch", "cim_mining_lds_bytes", "cim_mining_sync_bytes", "cim_detect_ws_bytes") or name in _LONG_RETURNING else c_int
     _lib = lib
     return lib
 
 
-VALUE_RETURNING = {"cim_maxpool2d_out_size", "cim_conv3x3_dx_parts", "cim_mining_sync_bytes", "cim_conv1x1_bwd_workspace", "cim_conv3x3_nchw_bwd_workspace", "cim_conv3x3_nchw_splits", "cim_gemm_small_splits", "cim_mining_lds_bytes", "cim_bn_act_bwd_chunks", "cim_gemm_pair_splits", "cim_roi_align_bwd_workspace", "cim_roi_align_bwd_scratch", "cim_detect_ws_bytes"}      # return a count, not a status
+_LONG_RETURNING = {"cim_segm_rle_decode_ws_bytes", "cim_segm_image_ws_bytes", "cim_segm_record_bytes", "cim_segm_accumulate_ws_bytes"}
+VALUE_RETURNING = _LONG_RETURNING | {"cim_segm_words"} | {"cim_maxpool2d_out_size", "cim_conv3x3_dx_parts", "cim_mining_sync_bytes", "cim_conv1x1_bwd_workspace", "cim_conv3x3_nchw_bwd_workspace", "cim_conv3x3_nchw_splits", "cim_gemm_small_splits", "cim_mining_lds_bytes", "cim_bn_act_bwd_chunks", "cim_gemm_pair_splits", "cim_roi_align_bwd_workspace", "cim_roi_align_bwd_scratch", "cim_detect_ws_bytes"}      # return a count, not a status
 
 
 # split counts / workspace sizes of the body's layers: pure functions of their integer arguments (their tuning switches are read

@@ -135,3 +135,29 @@ def make_scores(n, num_classes, rng):
     det = perm() * np.float32(2.0 ** -6)
     iou = perm()
     return cls, det, iou
+
+
+def make_segm_image(rng, h, w, num_cats, n_gt, n_prop, n_det, crowd_frac=0.0, score_levels=0, min_side=6):
+    """One seeded instance-segmentation image for the evaluator (cim_amd.segm_eval): n_gt ground-truth masks and n_prop
+    proposal masks (the ground truths are the first proposals; make_masks draws a quarter of the rest inside earlier ones,
+    so IoUs spread over (0, 1]), and n_det detections = (proposal index, category, fp32 score).  Ground-truth categories
+    are drawn from 1..num_cats, a detection takes a ground truth's category 3 times in 4; a tenth of the annotation areas
+    differ from the pixel count (COCO's `area` field is the polygon's); crowd_frac of the ground truths are crowd regions;
+    score_levels > 0 quantises scores to that many values so that ties occur."""
+    masks, boxes = make_masks(max(n_prop, n_gt), h, w, rng, min_side=min_side)
+    gt_cat = rng.randint(1, num_cats + 1, size=n_gt)
+    area = masks[:n_gt].reshape(n_gt, h * w).sum(1).astype(np.float64)
+    odd = rng.rand(n_gt) < 0.1
+    area[odd] *= rng.uniform(0.3, 3.0, size=int(odd.sum()))
+    crowd = (rng.rand(n_gt) < crowd_frac).astype(np.int32)
+    idx = rng.randint(0, masks.shape[0], size=n_det)
+    own = rng.rand(n_det) < 0.75
+    dcat = rng.randint(1, num_cats + 1, size=n_det)
+    if n_gt:
+        dcat[own] = gt_cat[rng.randint(0, n_gt, size=int(own.sum()))]
+    if score_levels:
+        score = (rng.randint(1, score_levels + 1, size=n_det) / np.float32(score_levels)).astype(np.float32)
+    else:
+        score = ((rng.permutation(1 << 20)[:n_det] + 1) / np.float32(1 << 20)).astype(np.float32)
+    return {"masks": masks, "boxes": boxes.astype(np.float32), "gt_cat": gt_cat, "gt_area": area, "gt_crowd": crowd,
+            "dt_idx": idx, "dt_cat": dcat, "dt_score": score}

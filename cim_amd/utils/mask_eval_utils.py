@@ -31,3 +31,23 @@ def mask_results_with_nms_and_limit_get_index(cfg, scores, boxes, DETECTIONS_PER
     cls_inds = _test._shift(_test._per_class(idx, count))
     out_scores, out_boxes = _test._flat(cls_boxes, cfg.MODEL.NUM_CLASSES)
     return out_scores, out_boxes, cls_boxes, cls_inds
+
+
+def coco_encode(mask):
+    """mask_eval_utils.py:113-116: pycocotools' COCOMask.encode(np.asfortranarray(mask)) with the counts decoded to str -
+    {'size': [h, w], 'counts': str}.  mask [h, w]: a bool / uint8 NumPy array (0 / 1 values) or device tensor (nonzero = 1);
+    the runs are found on the device (cim_amd.segm_eval), the string is built on the host (cim_amd.utils.rle)."""
+    from .. import segm_eval
+    if torch.is_tensor(mask):
+        m = mask
+    else:
+        a = np.asarray(mask)
+        if a.dtype != np.bool_:
+            if a.dtype != np.uint8:
+                raise TypeError("coco_encode: mask must be bool or uint8 (pycocotools encodes uint8), got %s" % a.dtype)
+            if a.size and a.max() > 1:
+                raise ValueError("coco_encode: uint8 mask with values other than 0 and 1")
+        m = torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(torch.device("cuda", torch.cuda.current_device()))
+    if m.dim() != 2:
+        raise ValueError("coco_encode: mask must be [h, w], got %s" % (tuple(m.shape),))
+    return segm_eval.rle_encode(m.unsqueeze(0))[0]

@@ -233,6 +233,65 @@ int cim_detect_nms_limit(const float* scores, int ld, const float* boxes, int N,
  * any.  out [C][2] i32 = (proposal, score bit pattern).  Same shape limits as above. */
 int cim_detect_corloc(const float* scores, int ld, int N, int C, int32_t* out, void* stream);
 
+/* ------------------------------------------------------------------ instance-segmentation evaluation (ABI-16 addition)
+ * Replaces pycocotools' mask.encode / decode / iou and COCOeval(..., 'segm').evaluateImg / accumulate as the reference runs
+ * them (tools/evaluation.py:72-145, 236-241; lib/datasets/json_inference.py:24-55; lib/utils/mask_eval_utils.py:113-116).
+ * Additive: cim_abi_version() stays 16.  Exactness contract and limits: DESIGN.md 4.12.
+ *
+ * Packed masks: uint64 [n][words], words = cim_segm_words(H, W) = ceil(H W / 64), pixel (y, x) at column-major position
+ * p = x H + y = bit p & 63 of word p >> 6; bits past H W are 0.
+ *   cim_segm_pack        [n_src, H, W] uint8 / bool masks (row-major, nonzero = 1) -> packed; idx [n] int64 (may be NULL =
+ *                        0..n-1) picks the source masks (an index outside [0, n_src) packs an empty mask)
+ *   cim_segm_area        pixel count per packed mask
+ *   cim_segm_rle_count   len [n] = number of COCO run counts per mask (column-major runs, alternating, starting with a
+ *                        zero-run, possibly empty: pycocotools' rleEncode)
+ *   cim_segm_rle_write   the counts (uint32) of mask i at counts[off[i] ...], len[i] of them (from cim_segm_rle_count)
+ *   cim_segm_rle_decode  counts -> packed masks; ws: cim_segm_rle_decode_ws_bytes(sum of len) bytes.  Pixels past the sum
+ *                        of a mask's counts stay 0, counts past H W are clipped.
+ * Per image (cim_segm_eval_image): detections in (image, category) groups, each sorted by -score (stable over the input
+ * order) and cut to its nd = min(n, maxDets[-1]); IoU inter / (area_d + area_g - inter) (inter / area_d for a crowd ground
+ * truth; 0 when inter == 0) in fp64 from integer popcounts; then evaluateImg's greedy matching per (group, area range,
+ * threshold).  meta int32: groups [n_groups][8] = (det_start, n_det, gt_start, n_gt, nd, rec_off, pair_off, 0) -
+ * det_start / gt_start index det_list / gt_list, rec_off is the group's byte offset in `records`
+ * (cim_segm_record_bytes(nd, n_gt, A, T) bytes, 8-byte aligned), pair_off its first entry of the nd x n_gt IoU block
+ * (pairs in all); then det_list [n_dl] (image detection indices, input order), gt_list [n_gl] (image ground-truth indices,
+ * input order), crowd [G].  gt_area [G] f64 is the annotations' `area`, gt_id [G] int64 their ids, iou_thrs [T] and
+ * area_rng [A][2] f64 the host's values.  ws: cim_segm_image_ws_bytes(D, G, pairs) bytes.  A record holds, in rank order:
+ * dtm int64 [A][T][nd] (matched ground-truth id, 0 = none), score f32 [nd], order int32 [nd], npig int32 [A], gt_order
+ * int32 [A][n_gt], dt_ignore uint8 [A][T][nd], gt_ignore uint8 [A][n_gt] (layout: csrc/segm_eval.hip rec_layout).
+ * Accumulate (cim_segm_accumulate): entries [n_entries][6] int64 = (record device address, nd, n_gt, first element,
+ * category index, 0), category-major and image-minor (ascending image id), one per (image, category) with a ground truth
+ * or a detection; cat_off [K + 1] the first element of each category (E elements in all); jobs [.][3] int64 = (start,
+ * lenA, lenB) of the bottom-up merge rounds of the per-image runs, round r's jobs at round_off[r] .. round_off[r + 1];
+ * rec_thrs [R] f64, max_dets [M] int32 (ascending).  Outputs (f64): precision / scores [T][R][K][A][M], recall
+ * [T][K][A][M], -1 where COCOeval leaves -1.  ws: cim_segm_accumulate_ws_bytes(E, K, A, T) bytes. */
+#define CIM_SEGM_MAX_HW (1 << 22)       /* pixels per mask */
+#define CIM_SEGM_MAX_GT 1024            /* ground truths per image */
+#define CIM_SEGM_MAX_T 16               /* IoU thresholds */
+#define CIM_SEGM_MAX_R 128              /* recall thresholds */
+#define CIM_SEGM_MAX_A 8                /* area ranges */
+#define CIM_SEGM_MAX_M 4                /* maxDets */
+/* detections per (image, category) and maxDets[-1]: <= CIM_DETECT_MAX_N */
+int cim_segm_words(int H, int W);
+int cim_segm_pack(const uint8_t* masks, const int64_t* idx, long long n_src, int n, int H, int W, uint64_t* packed, void* stream);
+int cim_segm_area(const uint64_t* packed, int n, int words, int32_t* area, void* stream);
+int cim_segm_rle_count(const uint64_t* packed, int n, int H, int W, int32_t* len, void* stream);
+int cim_segm_rle_write(const uint64_t* packed, int n, int H, int W, const int64_t* off, const int32_t* len, uint32_t* counts,
+                       void* stream);
+long long cim_segm_rle_decode_ws_bytes(long long total_counts);
+int cim_segm_rle_decode(const uint32_t* counts, const int64_t* off, const int32_t* len, int n, int H, int W, void* ws,
+                        uint64_t* packed, void* stream);
+long long cim_segm_image_ws_bytes(int D, int G, long long pairs);
+long long cim_segm_record_bytes(int nd, int ng, int A, int T);
+int cim_segm_eval_image(const uint64_t* dt_packed, int D, const uint64_t* gt_packed, int G, int words, const float* dt_score,
+                        const int32_t* meta, int n_groups, int n_dl, int n_gl, long long pairs, const double* gt_area,
+                        const int64_t* gt_id, const double* iou_thrs, int T, const double* area_rng, int A, void* ws,
+                        void* records, void* stream);
+long long cim_segm_accumulate_ws_bytes(long long E, int K, int A, int T);
+int cim_segm_accumulate(const int64_t* entries, int n_entries, long long E, int K, const int64_t* cat_off, const int64_t* jobs,
+                        const int64_t* round_off, int rounds, const double* rec_thrs, int R, const int32_t* max_dets, int M,
+                        int A, int T, void* ws, double* precision, double* recall, double* scores, void* stream);
+
 /* ------------------------------------------------------------------ network-input image (f-3: the data side of the step)
  * Replaces prep_im_for_blob(flag="ToTensor"), lib/utils/blob.py:93-147, called from lib/roi_data/minibatch.py:109-150
  * (training) and lib/core/test.py:464-473 via get_image_blob (inference):
