@@ -187,21 +187,46 @@ __device__ __forceinline__ void small_put_part(const SmallArgs& g, int row, int 
         g.mpart[((size_t)g.mparts + group) * g.M + row] = s2;
     }
 }
-// Epilogue of a wave's 32 x 32 accumulator tile: lane holds rows 8*(r/4) + 4*(lane/32) + r%4, column lane%32
-__device__ __forceinline__ void small_epilogue(const SmallArgs& g, const f32x16& acc, int row0, int col0, int lane, int split) {
-    const int col = col0 + (lane & 31);
-    if (g.splits > 1) {
-        if (col < g.N) {
+// Column mappings of the epilogue: tile column -> (in range, column of C) and the partial-sum group of a 32-column half of the tile.
+struct ColIdentity {
+    static constexpr bool splitk = true;
+    int N;
+    __device__ __forceinline__ bool in(int c) const { return c < N; }
+    __device__ __forceinline__ int col(int c) const { return c; }
+    __device__ __forceinline__ int group(int c0) const { return c0 >> 5; }
+};
+// conv3x3_dx2_kernel: column c of pixel class (py, px) is the input pixel (2 yc + py, 2 xc + px), groups numbered class by class
+struct ColParity {
+    static constexpr bool splitk = false;      // (the kernel never splits K)
+    int Wc, W, py, px, Nc, group0;
+    __device__ __forceinline__ bool in(int c) const { return c < Nc; }
+    __device__ __forceinline__ int col(int c) const {
+        const int yc = c / Wc, xc = c - yc * Wc;
+        return (2 * yc + py) * W + 2 * xc + px;
+    }
+    __device__ __forceinline__ int group(int c0) const { return group0 + (c0 >> 5); }
+};
+// Epilogue of a wave's 32 x 32 accumulator tile: lane holds rows 8*(r/4) + 4*(lane/32) + r%4, column lane%32.  Split K: the partial tile
+// goes to the workspace (small_splitk_reduce*_kernel finishes it).
+template <class Map>
+__device__ __forceinline__ void small_epilogue(const SmallArgs& g, const f32x16& acc, int row0, int col0, int lane, int split, const Map& cm) {
+#if CIM_SMALL_ABL == 2       /* ablation: no stores (one lane of a tile that does not exist keeps the product alive) */
+    if (row0 + lane >= 0) return;
+#endif
+    const int nc = col0 + (lane & 31);      // (the range test where it is used: hoisted, it changed the generated code)
+    if (Map::splitk && g.splits > 1) {
+        if (cm.in(nc)) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = row0 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
-                if (row < g.M) g.ws[((size_t)split * g.M + row) * g.N + col] = acc[r];
+                if (row < g.M) g.ws[((size_t)split * g.M + row) * g.N + cm.col(nc)] = acc[r];
             }
         }
         return;
     }
+    const int col = cm.col(nc);
     if (g.mpart == nullptr) {
-        if (col < g.N) {
+        if (cm.in(nc)) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = row0 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
@@ -214,8 +239,8 @@ __device__ __forceinline__ void small_epilogue(const SmallArgs& g, const f32x16&
     for (int r = 0; r < 16; ++r) {          // (every lane takes part in the row sums)
         const int row = row0 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
         float s1 = 0.0f, s2 = 0.0f;
-        if (col < g.N && row < g.M) small_finish(g, row, col, acc[r], s1, s2);
-        small_put_part(g, row, col0 >> 5, lane, s1, s2);
+        if (cm.in(nc) && row < g.M) small_finish(g, row, col, acc[r], s1, s2);
+        small_put_part(g, row, cm.group(col0), lane, s1, s2);
     }
 }
 
@@ -317,11 +342,7 @@ __global__ __launch_bounds__(128 * WN) void gemm_small_kernel(const SmallArgs g)
 #undef SM_PUT
 #undef SM_MMA
 
-#if CIM_SMALL_ABL == 2       /* ablation: no stores (one lane of a tile that does not exist keeps the product alive) */
-    if (m0 + wm * 32 + lane < 0) small_epilogue(g, acc, m0 + wm * 32, n0 + wn * 32, lane, split);
-#else
-    small_epilogue(g, acc, m0 + wm * 32, n0 + wn * 32, lane, split);
-#endif
+    small_epilogue(g, acc, m0 + wm * 32, n0 + wn * 32, lane, split, ColIdentity{g.N});
 }
 
 // Round 6, measured and dropped: a TILE-WALKING form of this kernel - R workgroups per CU (the LDS request padded so that exactly R
@@ -613,10 +634,7 @@ __global__ __launch_bounds__(256) void conv3x3_small_kernel(const SmallArgs g, c
     }
 #undef C3_PUT
 #undef C3_MMA
-#if CIM_SMALL_ABL == 2
-    if (m0 + wm * 32 + lane < 0)
-#endif
-    small_epilogue(g, acc, m0 + wm * 32, n0 + wn * 32, lane, split);
+    small_epilogue(g, acc, m0 + wm * 32, n0 + wn * 32, lane, split, ColIdentity{g.N});
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -629,34 +647,9 @@ __global__ __launch_bounds__(256) void conv3x3_small_kernel(const SmallArgs g, c
 // only:  K' = cout x {1, 2, 2, 4},  k' = co T + j,  tap j of class -> (ky, kx);  the pixel (yc, xc) of a class is the input
 // pixel (2 yc + py, 2 xc + px) and reads dY[co][yc + oy][xc + ox] with oy = [py and ky == 0], ox = [px and kx == 0].
 // No split-K (the longest class walks 4 cout / 32 slabs: 16 / 32 at res3 / res4) and no reduce launch; the epilogue (producer's
-// BatchNorm + ReLU backward, its affine partial sums) is small_epilogue's with the column mapped back to the map:
+// BatchNorm + ReLU backward, its affine partial sums) is small_epilogue's with the column mapped back to the map (ColParity):
 // partial-sum groups are numbered class by class (cim_conv3x3_dx_parts).
 struct Dx2Geom { int H, W, Ho, Wo, cin, cout; int first[5]; int tiles_n[4]; int group0[4]; };
-struct ColMap { int Wc, W, py, px, Nc, group0; };
-
-__device__ __forceinline__ void small_epilogue_mapped(const SmallArgs& g, const f32x16& acc, int row0, int col0, int lane, const ColMap& cm) {
-    const int nc = col0 + (lane & 31);
-    const bool in = nc < cm.Nc;
-    const int yc = nc / cm.Wc, xc = nc - yc * cm.Wc;
-    const int col = (2 * yc + cm.py) * cm.W + 2 * xc + cm.px;
-    if (g.mpart == nullptr) {
-        if (in) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = row0 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
-                if (row < g.M) small_finish(g, row, col, acc[r]);
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = row0 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
-        float s1 = 0.0f, s2 = 0.0f;
-        if (in && row < g.M) small_finish(g, row, col, acc[r], s1, s2);
-        small_put_part(g, row, cm.group0 + (col0 >> 5), lane, s1, s2);
-    }
-}
 
 __global__ __launch_bounds__(256) void conv3x3_dx2_kernel(const SmallArgs g, const Dx2Geom c) {
     CIM_BODY_PRIO();
@@ -769,8 +762,7 @@ __global__ __launch_bounds__(256) void conv3x3_dx2_kernel(const SmallArgs g, con
     }
 #undef D2_PUT
 #undef D2_MMA
-    const ColMap cm{Wc, c.W, py, px, Nc, c.group0[cls]};
-    small_epilogue_mapped(g, acc, m0 + wm * 32, n0 + wn * 32, lane, cm);
+    small_epilogue(g, acc, m0 + wm * 32, n0 + wn * 32, lane, 0, ColParity{Wc, c.W, py, px, Nc, c.group0[cls]});
 }
 
 // w [Cout][Cin][9] -> wt [Cout][9][Cin] (the data gradient's A operand, M-contiguous): one workgroup per output channel,
@@ -805,10 +797,32 @@ __global__ __launch_bounds__(256) void conv3x3_wt_multi_kernel(const WtTable t) 
     }
 }
 
-static void set_input_bn(SmallArgs& g, const InputBn* in_bn) {
-    if (in_bn == nullptr) return;
-    g.mask = in_bn->y; g.mgamma = in_bn->gamma; g.mvar = in_bn->var; g.meps = in_bn->eps;
-    g.mxr = in_bn->xr; g.mmean = in_bn->mean; g.mpart = in_bn->part; g.mparts = (g.N + 31) / 32;
+// The arguments of every small-tile launch: the product, the input-side BatchNorm backward (in_bn) and the output-side epilogue
+// (x_raw, BatchNorm, residual, ReLU).
+SmallArgs small_args(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, int splits, float* ws,
+                     const InputBn* in_bn, float* x_raw = nullptr, const float* gamma = nullptr, const float* beta = nullptr,
+                     const float* mean = nullptr, const float* var = nullptr, float eps = 0.f, const float* residual = nullptr, int relu = 0) {
+    SmallArgs g{};
+    g.A = A; g.B = B; g.C = C; g.Xraw = x_raw;
+    g.gamma = gamma; g.beta = beta; g.mean = mean; g.var = var; g.res = residual; g.eps = eps;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+    g.relu = relu; g.bn = gamma != nullptr;
+    g.splits = splits; g.ws = ws;
+    if (in_bn) {
+        g.mask = in_bn->y; g.mgamma = in_bn->gamma; g.mvar = in_bn->var; g.meps = in_bn->eps;
+        g.mxr = in_bn->xr; g.mmean = in_bn->mean; g.mpart = in_bn->part; g.mparts = (N + 31) / 32;
+    }
+    return g;
+}
+// 256-thread launch with `lds` bytes of dynamic LDS (the limit raised first where it is above 48 KB)
+template <class Kernel, class... Args>
+int launch_lds(Kernel kern, dim3 grid, size_t lds, hipStream_t st, const Args&... args) {
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, args...);
+    return 0;
 }
 static void launch_splitk_reduce(const SmallArgs& g, hipStream_t st) {
     if (g.mpart) {
@@ -858,33 +872,15 @@ extern "C" int cim_gemm_small_splits(int M, int N, int K) {
 static int gemm_small_impl(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
                            int a_mcontig, int b_kcontig, float* x_raw, const float* gamma, const float* beta,
                            const float* mean, const float* var, float eps, const float* residual, int relu, int splits,
-                           float* workspace, void* stream, const InputBn* in_bn, int res_w = 0);
-
-extern "C" int cim_gemm_small_f32(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
-                                  int a_mcontig, int b_kcontig, float* x_raw, const float* gamma, const float* beta,
-                                  const float* mean, const float* var, float eps, const float* residual, int relu, int splits,
-                                  float* workspace, void* stream) {
-    return gemm_small_impl(A, B, C, M, N, K, lda, ldb, ldc, a_mcontig, b_kcontig, x_raw, gamma, beta, mean, var, eps, residual, relu,
-                           splits, workspace, stream, nullptr);
-}
-
-static int gemm_small_impl(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
-                           int a_mcontig, int b_kcontig, float* x_raw, const float* gamma, const float* beta,
-                           const float* mean, const float* var, float eps, const float* residual, int relu, int splits,
-                           float* workspace, void* stream, const InputBn* in_bn, int res_w) {
+                           float* workspace, void* stream, const InputBn* in_bn, int res_w = 0) {
     CIM_CHECK_ARG(res_w == 0 || (residual && res_w > 0 && N % res_w == 0 && ldc == N));
     CIM_CHECK_ARG(A && B && C && M > 0 && N > 0 && K > 0 && lda > 0 && ldb > 0 && ldc >= N && splits >= 1);
     CIM_CHECK_ARG((gamma == nullptr) == (beta == nullptr) && (gamma == nullptr) == (mean == nullptr) && (gamma == nullptr) == (var == nullptr));
     CIM_CHECK_ARG(splits == 1 || workspace);
-    SmallArgs g{};
-    g.A = A; g.B = B; g.C = C; g.Xraw = x_raw;
-    g.gamma = gamma; g.beta = beta; g.mean = mean; g.var = var; g.res = residual; g.eps = eps;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.a_mcontig = a_mcontig; g.b_kcontig = b_kcontig; g.relu = relu; g.bn = gamma != nullptr;
-    g.splits = splits; g.ws = workspace; g.colbias = nullptr;
+    SmallArgs g = small_args(A, B, C, M, N, K, lda, ldb, ldc, splits, workspace, in_bn, x_raw, gamma, beta, mean, var, eps, residual, relu);
+    g.a_mcontig = a_mcontig; g.b_kcontig = b_kcontig;
     g.res_w = res_w;
     if (res_w) { g.res_ws = (res_w + 1) / 2; g.res_hw = ((N / res_w + 1) / 2) * g.res_ws; }
-    set_input_bn(g, in_bn);
     const long long tiles = (long long)((M + SBM - 1) / SBM) * ((N + SBN - 1) / SBN);
     CIM_CHECK_ARG(tiles * 2 < (1ll << 31) && splits <= 65535 && M <= 65535);
     // (the loaders address the operands through buffer resources with 32-bit byte offsets; OOB = 2^31 - 1 must lie behind them)
@@ -901,17 +897,21 @@ static int gemm_small_impl(const float* A, const float* B, float* C, int M, int 
     return 0;
 }
 
+extern "C" int cim_gemm_small_f32(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
+                                  int a_mcontig, int b_kcontig, float* x_raw, const float* gamma, const float* beta,
+                                  const float* mean, const float* var, float eps, const float* residual, int relu, int splits,
+                                  float* workspace, void* stream) {
+    return gemm_small_impl(A, B, C, M, N, K, lda, ldb, ldc, a_mcontig, b_kcontig, x_raw, gamma, beta, mean, var, eps, residual, relu,
+                           splits, workspace, stream, nullptr);
+}
+
 // Y[M][N] = X[M][K] . W[N][K]^T + bias[N]  (nn.Linear on the small-tile fp32-MFMA GEMM): the eight scoring heads of
 // lib/modeling/heads.py:194-219 as ONE product against their concatenated weights (N = 8 (C + 1) = 168 / 648 columns).
 extern "C" int cim_linear_bias_f32(const float* X, const float* W, const float* bias, float* Y, int M, int N, int K, int splits,
                                    float* workspace, void* stream) {
     CIM_CHECK_ARG(X && W && Y && M > 0 && N > 0 && K > 0 && splits >= 1 && splits <= 65535 && (splits == 1 || workspace));
-    SmallArgs g{};
-    g.A = X; g.B = W; g.C = Y; g.Xraw = nullptr;
-    g.gamma = g.beta = g.mean = g.var = g.res = nullptr; g.eps = 0.f;
-    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N;
-    g.a_mcontig = 0; g.b_kcontig = 1; g.relu = 0; g.bn = 0;
-    g.splits = splits; g.ws = workspace; g.colbias = bias;
+    SmallArgs g = small_args(X, W, Y, M, N, K, K, K, N, splits, workspace, nullptr);
+    g.b_kcontig = 1; g.colbias = bias;
     hipStream_t st = cim::as_stream(stream);
     launch_small<false, true>(g, splits, st, false);
     if (splits > 1) {
@@ -964,6 +964,18 @@ __global__ __launch_bounds__(256) void small_axpy_kernel(float* __restrict__ y, 
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) y[i] += x[i];
 }
+// The weight gradient of a batch: image 0's product goes to dw, every later image's to the workspace behind the split-K area (sp
+// partial products of n floats) and is added to dw.  product(b, out) enqueues image b's product on st.
+template <class Product>
+int dw_over_images(int B, float* dw, float* ws_dw, int sp, size_t n, hipStream_t st, Product product) {
+    for (int b = 0; b < B && dw; ++b) {
+        float* out = b == 0 ? dw : ws_dw + (size_t)sp * n;
+        const int rc = product(b, out);
+        if (rc) return rc;
+        if (b) hipLaunchKernelGGL(small_axpy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dw, out, n);
+    }
+    return 0;
+}
 }  // namespace
 
 extern "C" int cim_conv1x1_bn_act_bwd(const float* dy, const float* y, const float* x_raw, const float* x, const float* w,
@@ -989,18 +1001,13 @@ extern "C" int cim_conv1x1_bn_act_bwd(const float* dy, const float* y, const flo
     int rc = dy_is_dconv ? 0 : cim_bn_act_bwd(dy, y, x_raw, gamma, mean, var, eps, dconv, dres, dgamma, dbeta, B, cout, hw, relu, stream);
     if (rc) return rc;
     ForkJoin fj(cim::as_stream(stream), cim::as_stream(side_stream), fork_event, join_event, dx && dw);
-    void* st_dw = fj.fork();                                   // the weight gradient next to the data gradient
-    for (int b = 0; b < B && dw; ++b) {                        // dW[cout, cin] = dconv . X^T  (K = hw)
-        const int sp = cim_gemm_small_splits(cout, cin, hw);
-        float* out = b == 0 ? dw : ws_dw + (size_t)sp * cout * cin;
-        rc = cim_gemm_small_f32(dconv + (size_t)b * cout * hw, x + (size_t)b * cin * hw, out, cout, cin, hw, hw, hw, cin, 0, 1,
-                                nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, 0, sp, ws_dw, st_dw);
-        if (rc) return rc;
-        if (b) {
-            const size_t n = (size_t)cout * cin;
-            hipLaunchKernelGGL(small_axpy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, cim::as_stream(st_dw), dw, out, n);
-        }
-    }
+    hipStream_t st_dw = fj.fork();                             // the weight gradient next to the data gradient
+    const int sp = cim_gemm_small_splits(cout, cin, hw);
+    rc = dw_over_images(B, dw, ws_dw, sp, (size_t)cout * cin, st_dw, [&](int b, float* out) {      // dW[cout, cin] = dconv . X^T  (K = hw)
+        return cim_gemm_small_f32(dconv + (size_t)b * cout * hw, x + (size_t)b * cin * hw, out, cout, cin, hw, hw, hw, cin, 0, 1,
+                                  nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, 0, sp, ws_dw, st_dw);
+    });
+    if (rc) return rc;
     for (int b = 0; b < B && dx; ++b) {                        // dX[cin, hw] = W^T . dconv  (x the BatchNorm + ReLU backward of the layer that made x)
         const InputBn ib{x + (size_t)b * cin * hw, in_gamma, in_var, in_eps, in_xr ? in_xr + (size_t)b * cin * hw : nullptr, in_mean,
                          in_part ? in_part + (size_t)b * 2 * ((hw + 31) / 32) * cin : nullptr};
@@ -1021,22 +1028,13 @@ namespace {
 int conv3x3_launch(int mode, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldc, const ConvGeom& c,
                    float* x_raw, const float* gamma, const float* beta, const float* mean, const float* var, float eps,
                    const float* residual, int relu, int splits, float* ws, hipStream_t st, int ksize = 3, const InputBn* in_bn = nullptr) {
-    SmallArgs g{};
-    g.A = A; g.B = B; g.C = C; g.Xraw = x_raw;
-    g.gamma = gamma; g.beta = beta; g.mean = mean; g.var = var; g.res = residual; g.eps = eps;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = 0; g.ldc = ldc;
-    g.a_mcontig = 0; g.b_kcontig = mode == CONV_DW; g.relu = relu; g.bn = gamma != nullptr;
-    g.splits = splits; g.ws = ws; g.colbias = nullptr;
-    set_input_bn(g, in_bn);
+    SmallArgs g = small_args(A, B, C, M, N, K, lda, 0, ldc, splits, ws, in_bn, x_raw, gamma, beta, mean, var, eps, residual, relu);
+    g.b_kcontig = mode == CONV_DW;
     const dim3 grid((unsigned)(((M + SBM - 1) / SBM) * ((N + SBN - 1) / SBN)), (unsigned)splits);
-    const size_t lds = sizeof(float) * 4 * CBK * SLD;
     auto kern = ksize == 7 ? conv3x3_small_kernel<CONV_FWD, 7>
                 : mode == CONV_FWD ? conv3x3_small_kernel<CONV_FWD> : mode == CONV_DX ? conv3x3_small_kernel<CONV_DX> : conv3x3_small_kernel<CONV_DW>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, g, c);
+    const int rc = launch_lds(kern, grid, sizeof(float) * 4 * CBK * SLD, st, g, c);
+    if (rc) return rc;
     if (splits > 1) launch_splitk_reduce(g, st);
     return 0;
 }
@@ -1163,12 +1161,8 @@ extern "C" int cim_conv3x3_wt_multi(const cim_wt_desc* descs, int n, void* strea
             max_cin = d.cin > max_cin ? d.cin : max_cin;
         }
         t.first[t.n] = total;
-        const size_t lds = sizeof(float) * max_cin * 9;
-        if (lds > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wt_multi_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL(conv3x3_wt_multi_kernel, dim3((unsigned)total), dim3(256), lds, st, t);
+        const int rc = launch_lds(conv3x3_wt_multi_kernel, dim3((unsigned)total), sizeof(float) * max_cin * 9, st, t);
+        if (rc) return rc;
     }
     CIM_CHECK_LAUNCH();
     return 0;
@@ -1202,35 +1196,24 @@ extern "C" int cim_conv3x3_nchw_bn_act_bwd(const float* dy, const float* y, cons
     if (rc) return rc;
     ForkJoin fj(st, cim::as_stream(side_stream), fork_event, join_event, dx && dw);
     hipStream_t st_dw = fj.fork();                             // the weight gradient next to the data gradient
-    for (int b = 0; b < B && dw; ++b) {                        // dW[cout][cin 9] = dconv . im2col(X)^T  (K = Ho Wo)
-        const int sp = cim_gemm_small_splits(cout, 9 * cin, hwo);
-        float* out = b == 0 ? dw : ws_dw + (size_t)sp * cout * cin * 9;
-        conv3x3_launch(CONV_DW, dconv + (size_t)b * cout * hwo, x + (size_t)b * cin * hw, out, cout, 9 * cin, hwo, hwo, 9 * cin, cw,
-                       nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, 0, sp, ws_dw, st_dw);
-        if (b) {
-            const size_t n = (size_t)cout * cin * 9;
-            hipLaunchKernelGGL(small_axpy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st_dw, dw, out, n);
-        }
-    }
+    const int sp = cim_gemm_small_splits(cout, 9 * cin, hwo);
+    rc = dw_over_images(B, dw, ws_dw, sp, (size_t)cout * cin * 9, st_dw, [&](int b, float* out) {   // dW[cout][cin 9] = dconv . im2col(X)^T  (K = Ho Wo)
+        return conv3x3_launch(CONV_DW, dconv + (size_t)b * cout * hwo, x + (size_t)b * cin * hw, out, cout, 9 * cin, hwo, hwo, 9 * cin, cw,
+                              nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, 0, sp, ws_dw, st_dw);
+    });
+    if (rc) return rc;
     if (dx && !wt_ready) hipLaunchKernelGGL(conv3x3_wt_kernel, dim3(cout), dim3(256), sizeof(float) * cin * 9, st, w, wt_own, cin);
     const int parts = cim_conv3x3_dx_parts(H, W, dilation == 1 ? stride : 1);
     for (int b = 0; b < B && dx; ++b) {                        // dX[cin][H W] = sum over (co, tap) W[co][ci][tap] dconv[co][shifted]
         const InputBn ib{x + (size_t)b * cin * hw, in_gamma, in_var, in_eps, in_xr ? in_xr + (size_t)b * cin * hw : nullptr, in_mean,
                          in_part ? in_part + (size_t)b * 2 * parts * cin : nullptr};
         if (stride == 2 && dilation == 1) {                    // by parity classes of the input pixels: a quarter of the MFMAs, no split-K
-            SmallArgs g{};
-            g.A = wt; g.B = dconv + (size_t)b * cout * hwo; g.C = dx + (size_t)b * cin * hw;
-            g.M = cin; g.N = hw; g.K = 9 * cout; g.lda = cin; g.ldb = 0; g.ldc = hw;
-            g.splits = 1;
-            set_input_bn(g, in_gamma ? &ib : nullptr);
+            SmallArgs g = small_args(wt, dconv + (size_t)b * cout * hwo, dx + (size_t)b * cin * hw, cin, hw, 9 * cout, cin, 0, hw, 1, nullptr,
+                                     in_gamma ? &ib : nullptr);
             g.mparts = parts;
             const Dx2Geom c2 = dx2_geom(cin, cout, H, W);
-            const size_t lds = sizeof(float) * 4 * CBK * SLD;
-            if (lds > 48 * 1024) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_dx2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return (int)e;
-            }
-            hipLaunchKernelGGL(conv3x3_dx2_kernel, dim3((unsigned)c2.first[4]), dim3(256), lds, st, g, c2);
+            rc = launch_lds(conv3x3_dx2_kernel, dim3((unsigned)c2.first[4]), sizeof(float) * 4 * CBK * SLD, st, g, c2);
+            if (rc) return rc;
             continue;
         }
         conv3x3_launch(CONV_DX, wt, dconv + (size_t)b * cout * hwo, dx + (size_t)b * cin * hw, cin, hw, 9 * cout, cin, hw, cx, nullptr,
