@@ -23,6 +23,7 @@ SIGNATURES = {
     "cim_roi_align_bwd": [_P, _P, _P] + [c_int] * 6 + [c_float, c_int, c_int, _P, _P],
     "cim_roi_align_maskcat_fwd": [_P, _P, _P, _P] + [c_int] * 6 + [c_float, c_int, c_int, _P],
     "cim_roi_align_maskcat_bwd": [_P, _P, _P, _P] + [c_int] * 6 + [c_float, c_int, c_int, _P, _P],
+    "cim_roi_align_forms": [c_int] * 9 + [_P] * 3,
     "cim_maxpool2d_out_size": [c_int, c_int, c_int, c_int],
     "cim_maxpool2d_fwd": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],
     "cim_maxpool2d_bwd": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],

@@ -312,11 +312,14 @@ __global__ __launch_bounds__(256) void roi_align_fwd_agg_kernel(const float* __r
     const float inv_count = 1.0f / reinterpret_cast<const float*>(box)[4];
     const float* __restrict__ fb = feat + (size_t)box[5] * H * W * C;
     if (tid == 0) {
-        int n = 0;
+        int n = 0;      // every row with a non-zero weight counts: more than s_rows holds takes the sample-order path below
         for (int y = ylo; y <= yhi; ++y)
-            if (wy[y] != 0.0f && n < 64) s_rows[n++] = y;
+            if (wy[y] != 0.0f) {
+                if (n < 64) s_rows[n] = y;
+                ++n;
+            }
         s_nrows = n;
-        s_over = 0;
+        s_over = n > 64;
     } else if (tid >= 64 && tid < 64 + P) {
         const int pw = tid - 64;
         int lo = xhi + 1, hi = xlo - 1;
@@ -1147,17 +1150,46 @@ __global__ __launch_bounds__(RG_NT) void roi_align_bwd_region_kernel(const float
     }
 }
 
+// Which kernels launch_fwd and launch_bwd take (CIM_ROI_FWD_* / CIM_ROI_BWD_* of include/cim_hip.h), decided here only and
+// reported on the host by cim_roi_align_forms.
+//   Forward, table-driven: the table workspace, 16-byte channel rows, 32-bit element offsets and bin rows of at most 64 map rows
+//   (maps of <= 64 rows, or <= 128 rows with P >= 4: H / P + 2 rows per bin); the row-sum kernel (two bin rows per workgroup) for
+//   maps up to 128 columns and P <= 7, the flat entry-list kernel otherwise.  Else the sample-order kernel.
+//   Backward, region form: the table workspace, 16-byte channel rows, 8-bit bin indices in the packed ranges (4 in the entry map:
+//   P <= 16), 32-bit element offsets, its LDS and region count.  It reuses tables the caller calls ready only when the forward at
+//   this geometry is a table form: every other forward leaves the workspace unwritten.
+struct RoiForms {
+    int fwd, bwd;
+    bool bwd_builds_tables;
+};
+
+static RoiForms roi_forms(int B, int C, int H, int W, int K, int P, bool maskcat, bool has_ws, bool tables_ready) {
+    RoiForms f;
+    const bool fwd_tables = has_ws && C % 4 == 0 && P <= FW_MAXP && (long long)H * W * C < (1ll << 30) &&
+                            (H <= 64 || (P >= 4 && H <= RS_MAXD));
+    if (fwd_tables)
+        f.fwd = (P <= 7 && W <= RS_MAXD) ? CIM_ROI_FWD_ROWSUM2 : CIM_ROI_FWD_AGG;
+    else
+        f.fwd = C % 4 == 0 ? CIM_ROI_FWD_SAMPLE4 : CIM_ROI_FWD_SAMPLE1;
+    const bool region = K > 0 && has_ws && C % 4 == 0 && P <= 16 && H < 256 && W < 256 &&
+                        (long long)K * P * P * (maskcat ? 2 : 1) * C < (1ll << 31) &&
+                        rg_lds_bytes(rg_group_size(K, B, C, H, W), P) <= 158 * 1024 &&
+                        ((H + RG_RH - 1) / RG_RH) * ((W + RG_RW - 1) / RG_RW) <= RG_MAXREG &&
+                        (long long)B * ((K + 63) / 64) * ((C + 255) / 256) * RG_MAXREG < (1ll << 31);
+    f.bwd = region ? CIM_ROI_BWD_REGION : C % 4 == 0 ? CIM_ROI_BWD_GENERIC4 : CIM_ROI_BWD_GENERIC1;
+    f.bwd_builds_tables = region && !(tables_ready && fwd_tables);
+    return f;
+}
+
 template <bool MASKCAT>
 int launch_fwd(const float* feat, const float* rois, const float* masks, float* out, int B, int C, int H, int W, int K,
                int P, float scale, int sr, int aligned, hipStream_t st, float* ws = nullptr) {
     if (K == 0) return 0;
     dim3 grid(K, P), block(256);
-    // table-driven kernels: need the table workspace, 16-byte channel rows and bin rows of at most 64 map rows (maps of <= 64 rows,
-    // or <= 128 rows with P >= 4: H / P + 2 rows per bin).  Row-sum kernel (two bin rows per workgroup) for maps up to 128 columns
-    // and P <= 7; the flat entry-list kernel otherwise.
-    if (ws != nullptr && C % 4 == 0 && P <= FW_MAXP && (long long)H * W * C < (1ll << 30) && (H <= 64 || (P >= 4 && H <= RS_MAXD))) {
+    const int form = roi_forms(B, C, H, W, K, P, MASKCAT, ws != nullptr, false).fwd;
+    if (form == CIM_ROI_FWD_ROWSUM2 || form == CIM_ROI_FWD_AGG) {
         hipLaunchKernelGGL(roi_tables_kernel, dim3(K), dim3(256), sizeof(float) * roi_rec_words(P, H, W), st, rois, ws, K, P, H, W, scale, sr, aligned);
-        if (P <= 7 && W <= RS_MAXD) {
+        if (form == CIM_ROI_FWD_ROWSUM2) {
             const int nth = C >= 1024 ? 256 : ((C / 4 + 63) / 64) * 64;       // narrow maps: no idle waves
             hipLaunchKernelGGL((roi_align_fwd_rowsum2_kernel<MASKCAT>), dim3(K, (P + 1) / 2), dim3(nth), 0, st, feat, masks, out, C, H, W, P, ws);
             return 0;
@@ -1168,7 +1200,7 @@ int launch_fwd(const float* feat, const float* rois, const float* masks, float* 
         return 0;
     }
     // sample-order kernel (the oracle's operation order: bit-identical; any C, P, map size)
-    if (C % 4 == 0)
+    if (form == CIM_ROI_FWD_SAMPLE4)
         hipLaunchKernelGGL((roi_align_fwd_kernel<4, MASKCAT>), grid, block, 0, st, feat, rois, masks, out, C, H, W, P,
                            scale, sr, aligned);
     else
@@ -1213,9 +1245,9 @@ __global__ __launch_bounds__(256) void roi_partial_reduce_kernel(const float4* _
 
 template <bool MASKCAT>
 static int launch_bwd_region(const float* go, const float* rois, const float* masks, float* gin, int B, int C, int H, int W,
-                             int K, int P, float scale, int sr, int aligned, float* ws, hipStream_t st, int tables_ready,
+                             int K, int P, float scale, int sr, int aligned, float* ws, hipStream_t st, bool build_tables,
                              float* scratch) {
-    if (!tables_ready)
+    if (build_tables)
         hipLaunchKernelGGL(roi_tables_kernel, dim3(K), dim3(256), sizeof(float) * roi_rec_words(P, H, W), st, rois, ws, K, P, H, W, scale, sr, aligned);
     const int ry = (H + RG_RH - 1) / RG_RH, rx = (W + RG_RW - 1) / RG_RW, n_regions = ry * rx;
     const RegionOrder order = region_order(ry, rx);
@@ -1243,20 +1275,18 @@ static int launch_bwd_region(const float* go, const float* rois, const float* ma
 template <bool MASKCAT>
 int launch_bwd(const float* go, const float* rois, const float* masks, float* gin, int B, int C, int H, int W, int K,
                int P, float scale, int sr, int aligned, float* ws, hipStream_t st, int tables_ready = 0, float* scratch = nullptr) {
-    // region form: 16-byte channel rows, the table workspace, 8-bit bin indices in the packed ranges, 32-bit element offsets.
-    // (With several ROI groups and no partial-map scratch the groups meet through atomicAdd: slow, but every entry point works.)
-    if (K > 0 && ws != nullptr && C % 4 == 0 && P <= 16 && H < 256 && W < 256 &&
-        (long long)K * P * P * (MASKCAT ? 2 : 1) * C < (1ll << 31) &&
-        rg_lds_bytes(rg_group_size(K, B, C, H, W), P) <= 158 * 1024 && ((H + RG_RH - 1) / RG_RH) * ((W + RG_RW - 1) / RG_RW) <= RG_MAXREG &&
-        (long long)B * ((K + 63) / 64) * ((C + 255) / 256) * RG_MAXREG < (1ll << 31))
-        return launch_bwd_region<MASKCAT>(go, rois, masks, gin, B, C, H, W, K, P, scale, sr, aligned, ws, st, tables_ready, scratch);
+    // region form (roi_forms).  With several ROI groups and no partial-map scratch the groups meet through atomicAdd: slow, but
+    // every entry point works.
+    const RoiForms f = roi_forms(B, C, H, W, K, P, MASKCAT, ws != nullptr, tables_ready != 0);
+    if (f.bwd == CIM_ROI_BWD_REGION)
+        return launch_bwd_region<MASKCAT>(go, rois, masks, gin, B, C, H, W, K, P, scale, sr, aligned, ws, st, f.bwd_builds_tables, scratch);
     // generic form (odd channel counts, no workspace, maps beyond the region form's limits): one thread per output element,
     // global atomics - the reference's own formulation
     hipError_t e = hipMemsetAsync(gin, 0, sizeof(float) * (size_t)B * H * W * C, st);
     if (e != hipSuccess) return (int)e;
     if (K == 0) return 0;
     dim3 grid(K, P), block(256);
-    if (C % 4 == 0)
+    if (f.bwd == CIM_ROI_BWD_GENERIC4)
         hipLaunchKernelGGL((roi_align_bwd_kernel<4, MASKCAT>), grid, block, 0, st, go, rois, masks, gin, C, H, W, P,
                            scale, sr, aligned);
     else
@@ -1318,6 +1348,17 @@ extern "C" int cim_roi_align_maskcat_fwd_ws(const float* feat, const float* rois
                               cim::as_stream(stream), workspace);
     if (rc) return rc;
     CIM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int cim_roi_align_forms(int B, int C, int H, int W, int K, int P, int maskcat, int has_workspace, int tables_ready,
+                                   int* fwd_form, int* bwd_form, int* bwd_builds_tables) {
+    CIM_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && K >= 0 && P > 0 && P <= 65535);
+    CIM_CHECK_ARG(fwd_form && bwd_form && bwd_builds_tables && (has_workspace || !tables_ready));
+    const RoiForms f = roi_forms(B, C, H, W, K, P, maskcat != 0, has_workspace != 0, tables_ready != 0);
+    *fwd_form = f.fwd;
+    *bwd_form = f.bwd;
+    *bwd_builds_tables = f.bwd_builds_tables ? 1 : 0;
     return 0;
 }
 

@@ -6,6 +6,7 @@ arguments, same NCHW tensor semantics, autograd-enabled).  Tensors are kept in
 torch.channels_last memory format internally: the HIP kernels (cim_amd/csrc/roi_align.hip)
 run with lanes along C.  No CPU path: CPU tensors raise.
 """
+import ctypes
 import os
 
 import torch
@@ -20,6 +21,19 @@ from . import gemm as _gemm
 # Forward kernel: the aggregated-weight form by default (each bin reads every pixel it touches once; a few ulp from
 # the sample-order sum); EXACT (CIM_ROI_FWD_EXACT=1) keeps the reference's sample order, bit-identical to the oracle.
 EXACT = os.environ.get("CIM_ROI_FWD_EXACT", "0") == "1"
+
+# kernel forms: CIM_ROI_FWD_* / CIM_ROI_BWD_* of include/cim_hip.h
+FWD_SAMPLE1, FWD_SAMPLE4, FWD_ROWSUM2, FWD_AGG = 0, 1, 2, 3
+BWD_GENERIC1, BWD_GENERIC4, BWD_REGION = 0, 1, 2
+
+
+def forms(B, C, H, W, K, P, maskcat=False, workspace=True, tables_ready=True):
+    """(forward form, backward form, whether the backward builds the per-ROI tables) the library takes at this geometry
+    (cim_roi_align_forms; host only).  The defaults are what autograd passes after the default forward."""
+    f, b, t = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.call("cim_roi_align_forms", B, C, H, W, K, P, int(bool(maskcat)), int(bool(workspace)), int(bool(tables_ready)),
+              ctypes.byref(f), ctypes.byref(b), ctypes.byref(t))
+    return f.value, b.value, bool(t.value)
 
 
 def _check(feat, rois):

@@ -52,11 +52,12 @@ int cim_roi_align_bwd(const float* grad_out, const float* rois, float* grad_in,
                       int B, int C, int H, int W, int K, int P,
                       float spatial_scale, int sampling_ratio, int aligned, float* workspace, void* stream);
 
-/* Forward with the backward's table workspace (cim_roi_align_bwd_workspace bytes): the per-ROI separable weight
- * tables are built once and every bin reads each pixel it touches ONCE with the aggregated weight
- * WY[ph][y]*WX[pw][x]/count - (gh+1)(gw+1) instead of 4*gh*gw loads per bin.  Same result up to the
- * reassociation of the sum (a few ulp; cim_roi_align_fwd keeps the reference's sample order bit for bit).
- * workspace == NULL behaves like cim_roi_align_fwd / cim_roi_align_maskcat_fwd. */
+/* Forward with the backward's table workspace (cim_roi_align_bwd_workspace bytes).  Where the geometry takes a table form
+ * (CIM_ROI_FWD_ROWSUM2 / CIM_ROI_FWD_AGG below) the per-ROI separable weight tables are built into the workspace once and
+ * every bin reads each pixel it touches ONCE with the aggregated weight WY[ph][y]*WX[pw][x]/count - (gh+1)(gw+1) instead
+ * of 4*gh*gw loads per bin.  Same result up to the reassociation of the sum (a few ulp; cim_roi_align_fwd keeps the
+ * reference's sample order bit for bit).  Any other geometry takes the sample-order kernel and leaves the workspace
+ * unwritten.  workspace == NULL behaves like cim_roi_align_fwd / cim_roi_align_maskcat_fwd. */
 int cim_roi_align_fwd_ws(const float* feat, const float* rois, float* out,
                          int B, int C, int H, int W, int K, int P,
                          float spatial_scale, int sampling_ratio, int aligned, float* workspace, void* stream);
@@ -64,8 +65,9 @@ int cim_roi_align_maskcat_fwd_ws(const float* feat, const float* rois, const flo
                                  int B, int C, int H, int W, int K, int P,
                                  float spatial_scale, int sampling_ratio, int aligned, float* workspace, void* stream);
 
-/* Backward with tables_ready != 0: `workspace` still holds the tables a *_fwd_ws call on the SAME rois / geometry
- * built (the aggregated-weight forward and the backward share them); 0 rebuilds them.
+/* Backward with tables_ready != 0: `workspace` is the one a *_fwd_ws call on the SAME rois / geometry was given; the
+ * backward reuses the tables in it only where that forward built them (a table form: cim_roi_align_forms) and builds them
+ * itself otherwise.  0 always rebuilds them.
  * scratch: cim_roi_align_bwd_scratch(K,B,C,H,W) bytes (0: none needed) for the per-ROI-group partial maps of the
  * region-form backward, which are then summed by one streaming pass; with scratch == NULL the groups meet in
  * grad_in through float atomics (device-scope float atomics run at ~90 G/s on MI355X: 2-3x slower end to end). */
@@ -94,8 +96,8 @@ int cim_roi_align_maskcat_fwd(const float* feat, const float* rois, const float*
  *   cim_wino7_pair_scales(kind 0))
  * that cim_gemm_pair_batched contracts with the filter image - `cat` is never stored (the two calls cim_roi_align_maskcat_fwd_ws
  * + cim_wino7_input_pair wrote and re-read its 4 * K * 49 * 2C bytes).  Bit-identical to those two calls.  P == 7, C % 8 == 0,
- * H, W <= 64; workspace: cim_roi_align_bwd_workspace(K,P,H,W) bytes, left holding the tables for cim_roi_align_maskcat_bwd_ws
- * (tables_ready = 1). */
+ * H, W <= 128; workspace: cim_roi_align_bwd_workspace(K,P,H,W) bytes, left holding the tables for cim_roi_align_bwd_ws /
+ * cim_roi_align_maskcat_bwd_ws (tables_ready = 1: these geometries are a table form of the forward, ROWSUM2). */
 int cim_roi_align_wino7_pair_fwd(const float* feat, const float* rois, const float* masks, void* V, const float* scale,
                                  int B, int C, int H, int W, int K, int Rs, int P, float spatial_scale, int sampling_ratio,
                                  int aligned, float* workspace, void* stream);
@@ -103,6 +105,30 @@ int cim_roi_align_wino7_pair_fwd(const float* feat, const float* rois, const flo
 int cim_roi_align_maskcat_bwd(const float* grad_cat, const float* rois, const float* masks, float* grad_in,
                               int B, int C, int H, int W, int K, int P,
                               float spatial_scale, int sampling_ratio, int aligned, float* workspace, void* stream);
+
+/* Kernel forms of the ROIAlign calls above (ABI-16 addition: cim_abi_version() stays 16).  Host only: no device work.
+ * For a geometry - maskcat != 0 for the mask-cat entry points, has_workspace != 0 when a table workspace is passed,
+ * tables_ready as given to the backward - it writes the forward kernel the fwd entry points take, the backward kernel
+ * the bwd entry points take, and 1 / 0 whether that backward builds the per-ROI tables itself.  The forward builds
+ * the tables exactly when its form is ROWSUM2 or AGG.  (K == 0 launches no forward kernel.)  Limits, DESIGN.md 4.3:
+ *   forward   ROWSUM2   workspace, C % 4 == 0, H W C < 2^30, H <= 64 or (P >= 4 and H <= 128); P <= 7 and W <= 128
+ *             AGG       the same table conditions with P <= 8; P == 8 or W > 128.  A bin row with more than 64 map rows
+ *                       or a bin with more than 64 (row, column) entries falls back to the sample order in the kernel.
+ *             SAMPLE4   otherwise, C % 4 == 0: the reference's sample order, bit-identical to it
+ *             SAMPLE1   otherwise
+ *   backward  REGION    K > 0, workspace, C % 4 == 0, P <= 16, H < 256, W < 256, at most 256 regions of 12 x 16 pixels,
+ *                       its LDS <= 158 KiB (P = 16 only with 64-ROI groups), K P P C (2C mask-cat) < 2^31
+ *             GENERIC4  otherwise, C % 4 == 0: the reference's scatter through global atomics
+ *             GENERIC1  otherwise */
+#define CIM_ROI_FWD_SAMPLE1 0      /* roi_align_fwd_kernel<1> */
+#define CIM_ROI_FWD_SAMPLE4 1      /* roi_align_fwd_kernel<4> */
+#define CIM_ROI_FWD_ROWSUM2 2      /* roi_tables_kernel + roi_align_fwd_rowsum2_kernel */
+#define CIM_ROI_FWD_AGG 3          /* roi_tables_kernel + roi_align_fwd_agg_kernel */
+#define CIM_ROI_BWD_GENERIC1 0     /* roi_align_bwd_kernel<1> */
+#define CIM_ROI_BWD_GENERIC4 1     /* roi_align_bwd_kernel<4> */
+#define CIM_ROI_BWD_REGION 2       /* roi_align_bwd_region_kernel (+ roi_partial_reduce_kernel: several ROI groups, scratch) */
+int cim_roi_align_forms(int B, int C, int H, int W, int K, int P, int maskcat, int has_workspace, int tables_ready,
+                        int* fwd_form, int* bwd_form, int* bwd_builds_tables);
 
 /* ------------------------------------------------------------------ mask IoU / containment maps (a-7)
  * Replaces lib/utils/mask_utils.py:6-18 (mask_iou) and :20-32 (mask_asymmetric_iou) as driven
