@@ -318,6 +318,38 @@ int cim_segm_accumulate(const int64_t* entries, int n_entries, long long E, int 
                         const int64_t* round_off, int rounds, const double* rec_thrs, int R, const int32_t* max_dets, int M,
                         int A, int T, void* ws, double* precision, double* recall, double* scores, void* stream);
 
+/* ------------------------------------------------------------------ training inputs from proposal masks (ABI-16 addition)
+ * Replaces tools/pre/generate_7_7_{voc,coco}.py:35-42 (tight boxes, PIL nearest resize to S x S) and the label assignment of
+ * tools/pre/AGPL_label_assign.py:154-180 / point_level_label_assign.py:66-93 (lib/utils/mask_utils.py:6-18).
+ * Additive: cim_abi_version() stays 16.  Exactness contract and limits: DESIGN.md 4.13.
+ *
+ * Shapes refused before any launch (-1): N < 1, H or W outside 1..65535 (the reference stores boxes as uint16),
+ * H W > CIM_SEGM_MAX_HW, S outside 1..CIM_PROP_MAX_S, P outside 0..CIM_PROP_MAX_POINTS, a class outside 0..C-1, a point
+ * outside the image (NumPy would wrap a negative index: a stated deviation).
+ * ws: cim_prop_ws_bytes(N, H W, P) bytes (P = 0 for the prepare call alone), 8-byte aligned, no initial content; one ws serves
+ * one call at a time.
+ *
+ * cim_prop_prepare: masks_u8 [N, H W] (non-zero = inside; pixel (y, x) at y W + x) ->
+ *   packed [words, N] uint64   exactly what cim_mask_pack writes (it is the one launch that reads masks_u8),
+ *   boxes [N, 4] int32         (xmin, ymin, xmax + 1, ymax + 1) of the set pixels,
+ *   area [N] int32, small [N, S, S] uint8 (0 / 1): the crop to the box resized as PIL's nearest filter does,
+ *   empty_flag [1] int32       0, or N - n for the first proposal n without a set pixel (its box, area and small are 0; the
+ *                              reference raises there, so nothing else is defined for such an image).
+ * Three launches (pack, extents from the words, resize); no host synchronisation.
+ *
+ * cim_prop_assign: packed / area as above; rows, cols, classes [P] int32 are HOST arrays, read before the call returns (the
+ * points travel in the kernel arguments), in the order the reference visits them; mat [N, C + 1] f32 out: at most one
+ * non-zero per row, the cluster number j + 1 of the LAST point j whose average mask the proposal overlaps by IoU > 0.5 in
+ * column class_j + 1, else P + 1 in column 0 when 0 < IoU <= 0.5 for some point; every row (1, 0, ...) when P = 0.
+ * Three launches (average masks, intersections, the sequential rule); no host synchronisation. */
+#define CIM_PROP_MAX_POINTS 256
+#define CIM_PROP_MAX_S 16
+long long cim_prop_ws_bytes(int N, int HW, int P);
+int cim_prop_prepare(const uint8_t* masks_u8, int N, int H, int W, int S, uint64_t* packed, int32_t* boxes, int32_t* area,
+                     uint8_t* small, int32_t* empty_flag, void* ws, void* stream);
+int cim_prop_assign(const uint64_t* packed, const int32_t* area, int N, int H, int W, const int32_t* rows, const int32_t* cols,
+                    const int32_t* classes, int P, int C, float* mat, void* ws, void* stream);
+
 /* ------------------------------------------------------------------ network-input image (f-3: the data side of the step)
  * Replaces prep_im_for_blob(flag="ToTensor"), lib/utils/blob.py:93-147, called from lib/roi_data/minibatch.py:109-150
  * (training) and lib/core/test.py:464-473 via get_image_blob (inference):
