@@ -11,6 +11,7 @@
 // 16 B/lane x 64-lane (1 KiB per wave) segment of one feature pixel's channel vector.
 #include <cstdlib>
 #include "common.h"
+#include "wino7_tile.h"
 #include "../../include/cim_hip.h"
 
 namespace {
@@ -79,6 +80,39 @@ __device__ __forceinline__ float4 vdiv(float4 a, float b) { return make_float4(a
 __device__ __forceinline__ void vzero(float& a) { a = 0.0f; }
 __device__ __forceinline__ void vzero(float4& a) { a = make_float4(0.f, 0.f, 0.f, 0.f); }
 
+// The in-range samples of output bin (ph, pw), in the oracle's order: f(ty, tx) per sample (an out-of-range one contributes 0).
+template <typename F>
+__device__ __forceinline__ void for_each_sample(const RoiGeom& g, int ph, int pw, int H, int W, F f) {
+    for (int iy = 0; iy < g.gh; ++iy) {
+        const float y = g.y1 + ph * g.bh + (iy + 0.5f) * g.bh / (float)g.gh;
+        const Tap ty = make_tap(y, H);
+        for (int ix = 0; ix < g.gw; ++ix) {
+            const float x = g.x1 + pw * g.bw + (ix + 0.5f) * g.bw / (float)g.gw;
+            const Tap tx = make_tap(x, W);
+            if (ty.valid && tx.valid) f(ty, tx);
+        }
+    }
+}
+
+// One output bin in the oracle's sample and operation order (FP contraction off: bit-identical to oracle/roi_align_ref.c) for the
+// VEC channels at fc = feature map of the ROI's image + channel.
+template <int VEC>
+__device__ __forceinline__ typename VecT<VEC>::type sample_bin(const float* __restrict__ fc, const RoiGeom& g, int ph, int pw, int C,
+                                                               int H, int W) {
+    using V = typename VecT<VEC>::type;
+    V acc;
+    vzero(acc);
+    for_each_sample(g, ph, pw, H, W, [&](const Tap& ty, const Tap& tx) {
+        const V v1 = *reinterpret_cast<const V*>(fc + ((size_t)ty.lo * W + tx.lo) * C);
+        const V v2 = *reinterpret_cast<const V*>(fc + ((size_t)ty.lo * W + tx.hi) * C);
+        const V v3 = *reinterpret_cast<const V*>(fc + ((size_t)ty.hi * W + tx.lo) * C);
+        const V v4 = *reinterpret_cast<const V*>(fc + ((size_t)ty.hi * W + tx.hi) * C);
+        const float w1 = ty.h * tx.h, w2 = ty.h * tx.l, w3 = ty.l * tx.h, w4 = ty.l * tx.l;
+        acc = vadd(acc, vadd(vadd(vadd(vmul(w1, v1), vmul(w2, v2)), vmul(w3, v3)), vmul(w4, v4)));
+    });
+    return vdiv(acc, g.count);
+}
+
 // grid = (K, P); block = 256 lanes along C.
 template <int VEC, bool MASKCAT>
 __global__ __launch_bounds__(256) void roi_align_fwd_kernel(const float* __restrict__ feat,
@@ -93,25 +127,7 @@ __global__ __launch_bounds__(256) void roi_align_fwd_kernel(const float* __restr
     const int OC = MASKCAT ? 2 * C : C;
     for (int c = threadIdx.x * VEC; c < C; c += blockDim.x * VEC) {
         for (int pw = 0; pw < P; ++pw) {
-            V acc;
-            vzero(acc);
-            for (int iy = 0; iy < g.gh; ++iy) {
-                const float y = g.y1 + ph * g.bh + (iy + 0.5f) * g.bh / (float)g.gh;
-                const Tap ty = make_tap(y, H);
-                for (int ix = 0; ix < g.gw; ++ix) {
-                    const float x = g.x1 + pw * g.bw + (ix + 0.5f) * g.bw / (float)g.gw;
-                    const Tap tx = make_tap(x, W);
-                    if (!(ty.valid && tx.valid)) continue;   // contributes 0
-                    const V v1 = *reinterpret_cast<const V*>(fb + ((size_t)ty.lo * W + tx.lo) * C + c);
-                    const V v2 = *reinterpret_cast<const V*>(fb + ((size_t)ty.lo * W + tx.hi) * C + c);
-                    const V v3 = *reinterpret_cast<const V*>(fb + ((size_t)ty.hi * W + tx.lo) * C + c);
-                    const V v4 = *reinterpret_cast<const V*>(fb + ((size_t)ty.hi * W + tx.hi) * C + c);
-                    const float w1 = ty.h * tx.h, w2 = ty.h * tx.l, w3 = ty.l * tx.h, w4 = ty.l * tx.l;
-                    const V val = vadd(vadd(vadd(vmul(w1, v1), vmul(w2, v2)), vmul(w3, v3)), vmul(w4, v4));
-                    acc = vadd(acc, val);
-                }
-            }
-            const V o = vdiv(acc, g.count);
+            const V o = sample_bin<VEC>(fb + c, g, ph, pw, C, H, W);
             float* dst = out + (((size_t)k * P + ph) * P + pw) * OC + c;
             *reinterpret_cast<V*>(dst) = o;
             if (MASKCAT) {
@@ -151,20 +167,13 @@ __global__ __launch_bounds__(256) void roi_align_bwd_kernel(const float* __restr
                 const float m = masks[((size_t)k * P + ph) * P + pw];
                 go = vadd(go, vmul(m, *reinterpret_cast<const V*>(src + C)));
             }
-            for (int iy = 0; iy < g.gh; ++iy) {
-                const float y = g.y1 + ph * g.bh + (iy + 0.5f) * g.bh / (float)g.gh;
-                const Tap ty = make_tap(y, H);
-                for (int ix = 0; ix < g.gw; ++ix) {
-                    const float x = g.x1 + pw * g.bw + (ix + 0.5f) * g.bw / (float)g.gw;
-                    const Tap tx = make_tap(x, W);
-                    if (!(ty.valid && tx.valid)) continue;
-                    const float w1 = ty.h * tx.h, w2 = ty.h * tx.l, w3 = ty.l * tx.h, w4 = ty.l * tx.l;
-                    atomic_add_vec(gb + ((size_t)ty.lo * W + tx.lo) * C + c, vdiv(vmul(w1, go), g.count));
-                    atomic_add_vec(gb + ((size_t)ty.lo * W + tx.hi) * C + c, vdiv(vmul(w2, go), g.count));
-                    atomic_add_vec(gb + ((size_t)ty.hi * W + tx.lo) * C + c, vdiv(vmul(w3, go), g.count));
-                    atomic_add_vec(gb + ((size_t)ty.hi * W + tx.hi) * C + c, vdiv(vmul(w4, go), g.count));
-                }
-            }
+            for_each_sample(g, ph, pw, H, W, [&](const Tap& ty, const Tap& tx) {
+                const float w1 = ty.h * tx.h, w2 = ty.h * tx.l, w3 = ty.l * tx.h, w4 = ty.l * tx.l;
+                atomic_add_vec(gb + ((size_t)ty.lo * W + tx.lo) * C + c, vdiv(vmul(w1, go), g.count));
+                atomic_add_vec(gb + ((size_t)ty.lo * W + tx.hi) * C + c, vdiv(vmul(w2, go), g.count));
+                atomic_add_vec(gb + ((size_t)ty.hi * W + tx.lo) * C + c, vdiv(vmul(w3, go), g.count));
+                atomic_add_vec(gb + ((size_t)ty.hi * W + tx.hi) * C + c, vdiv(vmul(w4, go), g.count));
+            });
         }
     }
 }
@@ -201,6 +210,27 @@ __device__ __forceinline__ void bin_range(float start, float bin, int P, int pos
 //   wy [P][H] | wx [P][W] | yr [H] | xr [W] | ylo yhi xlo xhi | count | batch      (4-byte words)
 // yr / xr: packed range of bins with a non-zero weight on that row / column: lo | hi << 8 | none << 16.
 __host__ __device__ __forceinline__ int roi_rec_words(int P, int H, int W) { return ((P + 1) * (H + W) + 6 + 3) & ~3; }
+
+// What the table-driven forwards read of ROI k's record.
+struct RoiRec {
+    const float* wy;      // [P][H]
+    const float* wx;      // [P][W]
+    const float* fb;      // feature map of the ROI's image
+    int ylo, yhi, xlo, xhi, ncols;
+    float inv_count;
+};
+__device__ __forceinline__ RoiRec roi_rec(const float* __restrict__ rec_all, const float* __restrict__ feat, int k, int C, int H,
+                                          int W, int P) {
+    RoiRec r;
+    r.wy = rec_all + (size_t)k * roi_rec_words(P, H, W);
+    r.wx = r.wy + P * H;
+    const int* box = reinterpret_cast<const int*>(r.wy + (P + 1) * (H + W));
+    r.ylo = box[0]; r.yhi = box[1]; r.xlo = box[2]; r.xhi = box[3];
+    r.ncols = max(r.xhi - r.xlo + 1, 0);
+    r.inv_count = 1.0f / reinterpret_cast<const float*>(box)[4];
+    r.fb = feat + (size_t)box[5] * H * W * C;
+    return r;
+}
 
 // The record is assembled in LDS (tables, packed ranges, bounding box through LDS atomics) and written to global memory
 // once, as one contiguous run: the first version went through global memory between its three phases (three dependent
@@ -273,18 +303,6 @@ typedef float ga_f2 __attribute__((ext_vector_type(2)));       // v_pk_fma_f32: 
 __device__ __forceinline__ ga_f2 ga_lo(const float4& v) { return ga_f2{v.x, v.y}; }
 __device__ __forceinline__ ga_f2 ga_hi(const float4& v) { return ga_f2{v.z, v.w}; }
 __device__ __forceinline__ ga_f2 ga_fma(float w, ga_f2 v, ga_f2 a) { return __builtin_elementwise_fma(ga_f2{w, w}, v, a); }
-#ifndef CIM_ROI_FU
-#define CIM_ROI_FU 8             // loads in flight per lane in the aggregated forward (4 or 8)
-#endif
-#ifndef CIM_ROI_FEXP
-#define CIM_ROI_FEXP 0           // ablations: 1 = no stores (0.131 ms incl. tables), 2 = no loads (0.100); product 0.157
-#endif
-#ifndef CIM_ROI_FZ
-#define CIM_ROI_FZ 1             // channel slices of the aggregated forward (grid.z); 2 / 4 (L2-sized slices) measured equal
-#endif
-#ifndef CIM_ROI_FNT
-#define CIM_ROI_FNT 1            // 1 = nontemporal stores of the pooled output
-#endif
 constexpr int FW_MAXP = 8;      // bins per axis the table-driven forwards take
 constexpr int AG_MAXE = 64;     // entries per (ph, pw) list kept in LDS; larger bins take the sample-order kernel
 
@@ -300,17 +318,13 @@ __global__ __launch_bounds__(256) void roi_align_fwd_agg_kernel(const float* __r
     __shared__ int s_n[FW_MAXP], s_xlo[FW_MAXP], s_nx[FW_MAXP];
     __shared__ int s_rows[64];                   // rows with a non-zero weight in this bin row
     __shared__ int s_nrows;
-    // grid.z splits the channels (CIM_ROI_FZ slices): with 2 slices one slice of the cfg2 map (2.9 MB) fits an XCD's 4 MB L2
     const int k = blockIdx.x, ph = blockIdx.y, tid = threadIdx.x, NTH = blockDim.x;
-    const int cslice = ((C / 4 + gridDim.z - 1) / gridDim.z) * 4;
-    const int c_first = blockIdx.z * cslice + tid * 4, c_end = min(C, (int)(blockIdx.z + 1) * cslice);
-    const float* rec = rec_all + (size_t)k * roi_rec_words(P, H, W);
-    const float* wy = rec + ph * H;
-    const float* wx = rec + P * H;
-    const int* box = reinterpret_cast<const int*>(rec + (P + 1) * (H + W));
-    const int ylo = box[0], yhi = box[1], xlo = box[2], xhi = box[3];
-    const float inv_count = 1.0f / reinterpret_cast<const float*>(box)[4];
-    const float* __restrict__ fb = feat + (size_t)box[5] * H * W * C;
+    const RoiRec R = roi_rec(rec_all, feat, k, C, H, W, P);
+    const float* wy = R.wy + ph * H;
+    const float* wx = R.wx;
+    const int ylo = R.ylo, yhi = R.yhi, xlo = R.xlo, xhi = R.xhi;
+    const float inv_count = R.inv_count;
+    const float* __restrict__ fb = R.fb;
     if (tid == 0) {
         int n = 0;      // every row with a non-zero weight counts: more than s_rows holds takes the sample-order path below
         for (int y = ylo; y <= yhi; ++y)
@@ -335,25 +349,9 @@ __global__ __launch_bounds__(256) void roi_align_fwd_agg_kernel(const float* __r
     const int OC = MASKCAT ? 2 * C : C;
     if (s_over) {      // block-uniform: a bin larger than the LDS list (ROI far larger than the map) -> sample by sample
         const RoiGeom g = roi_geom(rois + 5 * (size_t)k, scale, P, sampling_ratio, aligned);
-        for (int c = c_first; c < c_end; c += NTH * 4) {
+        for (int c = tid * 4; c < C; c += NTH * 4) {
             for (int pw = 0; pw < P; ++pw) {
-                float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-                for (int iy = 0; iy < g.gh; ++iy) {
-                    const float y = g.y1 + ph * g.bh + (iy + 0.5f) * g.bh / (float)g.gh;
-                    const Tap ty = make_tap(y, H);
-                    for (int ix = 0; ix < g.gw; ++ix) {
-                        const float x = g.x1 + pw * g.bw + (ix + 0.5f) * g.bw / (float)g.gw;
-                        const Tap tx = make_tap(x, W);
-                        if (!(ty.valid && tx.valid)) continue;
-                        const float4 v1 = *reinterpret_cast<const float4*>(fb + ((size_t)ty.lo * W + tx.lo) * C + c);
-                        const float4 v2 = *reinterpret_cast<const float4*>(fb + ((size_t)ty.lo * W + tx.hi) * C + c);
-                        const float4 v3 = *reinterpret_cast<const float4*>(fb + ((size_t)ty.hi * W + tx.lo) * C + c);
-                        const float4 v4 = *reinterpret_cast<const float4*>(fb + ((size_t)ty.hi * W + tx.hi) * C + c);
-                        const float w1 = ty.h * tx.h, w2 = ty.h * tx.l, w3 = ty.l * tx.h, w4 = ty.l * tx.l;
-                        acc = vadd(acc, vadd(vadd(vadd(vmul(w1, v1), vmul(w2, v2)), vmul(w3, v3)), vmul(w4, v4)));
-                    }
-                }
-                const float4 o = vdiv(acc, g.count);
+                const float4 o = sample_bin<4>(fb + c, g, ph, pw, C, H, W);
                 float* dst = out + (((size_t)k * P + ph) * P + pw) * OC + c;
                 *reinterpret_cast<float4*>(dst) = o;
                 if (MASKCAT) *reinterpret_cast<float4*>(dst + C) = vmul(masks[((size_t)k * P + ph) * P + pw], o);
@@ -372,19 +370,14 @@ __global__ __launch_bounds__(256) void roi_align_fwd_agg_kernel(const float* __r
         }
     }
     __syncthreads();
-    for (int c = c_first; c < c_end; c += NTH * 4) {
+    for (int c = tid * 4; c < C; c += NTH * 4) {
         const float* __restrict__ fc = fb + c;
         for (int pw = 0; pw < P; ++pw) {
             const int2* el = ent + pw * AG_MAXE;
-#if CIM_ROI_FEXP == 2
-            const int n = 0;
-#else
             const int n = s_n[pw];
-#endif
             ga_f2 al = {0.f, 0.f}, ah = {0.f, 0.f};
             int i = 0;
-#if CIM_ROI_FU == 8
-            for (; i + 8 <= n; i += 8) {
+            for (; i + 8 <= n; i += 8) {      // 8 loads in flight per lane, then the 4 and 1 tails
                 int2 e[8];
                 float4 v[8];
 #pragma unroll
@@ -398,7 +391,6 @@ __global__ __launch_bounds__(256) void roi_align_fwd_agg_kernel(const float* __r
                     ah = ga_fma(w, ga_hi(v[j]), ah);
                 }
             }
-#endif
             for (; i + 4 <= n; i += 4) {
                 const int2 e0 = el[i], e1 = el[i + 1], e2 = el[i + 2], e3 = el[i + 3];
                 const float4 v0 = *reinterpret_cast<const float4*>(fc + e0.x);
@@ -419,22 +411,104 @@ __global__ __launch_bounds__(256) void roi_align_fwd_agg_kernel(const float* __r
             }
             const float4 acc = make_float4(al.x, al.y, ah.x, ah.y);
             float* dst = out + (((size_t)k * P + ph) * P + pw) * OC + c;
-#if CIM_ROI_FEXP == 1      /* ablation: no stores */
-            if (acc.x != 123.456f) continue;
-#endif
-#if CIM_ROI_FEXP == 2      /* ablation: no loads (stores only) */
-#endif
-#if CIM_ROI_FNT
             typedef float ga_f4 __attribute__((ext_vector_type(4)));
             __builtin_nontemporal_store(ga_f4{acc.x, acc.y, acc.z, acc.w}, reinterpret_cast<ga_f4*>(dst));
             if (MASKCAT) {
                 const float4 mo = vmul(masks[((size_t)k * P + ph) * P + pw], acc);
                 __builtin_nontemporal_store(ga_f4{mo.x, mo.y, mo.z, mo.w}, reinterpret_cast<ga_f4*>(dst + C));
             }
-#else
-            *reinterpret_cast<float4*>(dst) = acc;
-            if (MASKCAT) *reinterpret_cast<float4*>(dst + C) = vmul(masks[((size_t)k * P + ph) * P + pw], acc);
-#endif
+        }
+    }
+}
+
+constexpr int RS_MAXD = 128;     // rows / columns of the map (round 6: was 64 - the reference's largest training scale gives 57 x 75 maps)
+
+// The row-sum core, shared by roi_align_fwd_rowsum2_kernel and the fused roi_align_wino7_pair_kernel: the two write the same bits
+// because they run these functions.
+// s_wx[xi][pw] = WX[pw][xlo + xi], zero for pw >= P: the column weights of one column as one padded row (whole workgroup).
+__device__ __forceinline__ void rs_fill_wx(float (*s_wx)[8], const RoiRec& R, int P, int W, int tid, int nth) {
+    for (int e = tid; e < R.ncols * 8; e += nth) {
+        const int xi = e >> 3, pw = e & 7;
+        s_wx[xi][pw] = pw < P ? R.wx[pw * W + R.xlo + xi] : 0.0f;
+    }
+}
+
+// The rows of the map with a non-zero weight in bin row ph0 or ph0 + 1, ascending, with their weights / count: a wave-wide
+// compaction, run by ONE whole wave (an ROI spans up to RS_MAXD = 128 rows: two passes of the wave).  Returns their number.
+__device__ __forceinline__ int rs_row_list(const RoiRec& R, int ph0, bool two, int H, int W, int lane, int* rows, float* wa,
+                                           float* wb) {
+    const float* wy0 = R.wy + ph0 * H;
+    const float* wy1 = wy0 + H;
+    int nrows = 0;
+    for (int y0 = R.ylo; y0 <= R.yhi; y0 += 64) {
+        const int y = y0 + lane;
+        float a = 0.0f, b = 0.0f;
+        if (y <= R.yhi) { a = wy0[y]; b = two ? wy1[y] : 0.0f; }
+        const bool on = y <= R.yhi && (a != 0.0f || b != 0.0f);
+        const unsigned long long m = __ballot(on);
+        if (on) {
+            const int n = nrows + __popcll(m & ((1ull << lane) - 1ull));
+            rows[n] = y * W; wa[n] = a * R.inv_count; wb[n] = b * R.inv_count;
+        }
+        nrows += __popcll(m);
+    }
+    return nrows;
+}
+
+// The column walk for the lane's 4 channels at fc: a (bin row ph0) and b (ph0 + 1), low and high channel pair of the 7 bins.
+__device__ __forceinline__ void rs_column_walk(const int* __restrict__ rows, const float* __restrict__ rwa,
+                                               const float* __restrict__ rwb, int nrows, int ncols, int xlo, int C,
+                                               const float* __restrict__ fc, const float (*s_wx)[8], ga_f2 (&al)[7], ga_f2 (&ah)[7],
+                                               ga_f2 (&bl)[7], ga_f2 (&bh)[7]) {
+#pragma unroll
+    for (int pw = 0; pw < 7; ++pw) al[pw] = ah[pw] = bl[pw] = bh[pw] = ga_f2{0.f, 0.f};
+    for (int xi = 0; xi < ncols; xi += 2) {
+        const bool pair = xi + 1 < ncols;            // wave-uniform; the odd last column is loaded twice, weight 0
+        const int x0 = (xlo + xi) * C, dx1 = pair ? C : 0;
+        ga_f2 ta0l = {0.f, 0.f}, ta0h = {0.f, 0.f}, ta1l = {0.f, 0.f}, ta1h = {0.f, 0.f};
+        ga_f2 tb0l = {0.f, 0.f}, tb0h = {0.f, 0.f}, tb1l = {0.f, 0.f}, tb1h = {0.f, 0.f};
+        int r = 0;
+        for (; r + 4 <= nrows; r += 4) {
+            float4 v0[4], v1[4];
+            float wa[4], wb[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float* src = fc + (size_t)rows[r + j] * C + x0;
+                v0[j] = *reinterpret_cast<const float4*>(src);
+                v1[j] = *reinterpret_cast<const float4*>(src + dx1);
+                wa[j] = rwa[r + j];
+                wb[j] = rwb[r + j];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                ta0l = ga_fma(wa[j], ga_lo(v0[j]), ta0l); ta0h = ga_fma(wa[j], ga_hi(v0[j]), ta0h);
+                ta1l = ga_fma(wa[j], ga_lo(v1[j]), ta1l); ta1h = ga_fma(wa[j], ga_hi(v1[j]), ta1h);
+                tb0l = ga_fma(wb[j], ga_lo(v0[j]), tb0l); tb0h = ga_fma(wb[j], ga_hi(v0[j]), tb0h);
+                tb1l = ga_fma(wb[j], ga_lo(v1[j]), tb1l); tb1h = ga_fma(wb[j], ga_hi(v1[j]), tb1h);
+            }
+        }
+        for (; r < nrows; ++r) {
+            const float* src = fc + (size_t)rows[r] * C + x0;
+            const float4 v0 = *reinterpret_cast<const float4*>(src);
+            const float4 v1 = *reinterpret_cast<const float4*>(src + dx1);
+            const float wa = rwa[r], wb = rwb[r];
+            ta0l = ga_fma(wa, ga_lo(v0), ta0l); ta0h = ga_fma(wa, ga_hi(v0), ta0h);
+            ta1l = ga_fma(wa, ga_lo(v1), ta1l); ta1h = ga_fma(wa, ga_hi(v1), ta1h);
+            tb0l = ga_fma(wb, ga_lo(v0), tb0l); tb0h = ga_fma(wb, ga_hi(v0), tb0h);
+            tb1l = ga_fma(wb, ga_lo(v1), tb1l); tb1h = ga_fma(wb, ga_hi(v1), tb1h);
+        }
+        const int xj = pair ? xi + 1 : xi;
+        const float4 wa0 = *reinterpret_cast<const float4*>(&s_wx[xi][0]), wb0 = *reinterpret_cast<const float4*>(&s_wx[xi][4]);
+        const float4 wa1 = *reinterpret_cast<const float4*>(&s_wx[xj][0]), wb1 = *reinterpret_cast<const float4*>(&s_wx[xj][4]);
+        const float m1 = pair ? 1.0f : 0.0f;
+        const float w0[7] = {wa0.x, wa0.y, wa0.z, wa0.w, wb0.x, wb0.y, wb0.z};
+        const float w1[7] = {m1 * wa1.x, m1 * wa1.y, m1 * wa1.z, m1 * wa1.w, m1 * wb1.x, m1 * wb1.y, m1 * wb1.z};
+#pragma unroll
+        for (int pw = 0; pw < 7; ++pw) {
+            al[pw] = ga_fma(w0[pw], ta0l, al[pw]); ah[pw] = ga_fma(w0[pw], ta0h, ah[pw]);
+            al[pw] = ga_fma(w1[pw], ta1l, al[pw]); ah[pw] = ga_fma(w1[pw], ta1h, ah[pw]);
+            bl[pw] = ga_fma(w0[pw], tb0l, bl[pw]); bh[pw] = ga_fma(w0[pw], tb0h, bh[pw]);
+            bl[pw] = ga_fma(w1[pw], tb1l, bl[pw]); bh[pw] = ga_fma(w1[pw], tb1h, bh[pw]);
         }
     }
 }
@@ -447,7 +521,6 @@ __global__ __launch_bounds__(256) void roi_align_fwd_agg_kernel(const float* __r
 // rows x (sum of the bins' column counts), ~23 % fewer at the benchmark's ROI sizes.  Two columns are in flight per
 // iteration (up to 8 loads per lane).  The 7 column weights of a column sit in LDS as one padded row (zero outside the
 // bin's range), so the bin update is 7 unconditional packed FMAs.
-constexpr int RS_MAXD = 128;     // rows / columns of the map (round 6: was 64 - the reference's largest training scale gives 57 x 75 maps)
 // Round 4, measured and dropped: workgroup = one ROI x one 256-channel slice (four waves = the four bin-row pairs) with the slices
 // pinned to XCDs, so that an XCD's L2 only sees its 1.45 MB of the 5.8 MB map (the calibrated FETCH_SIZE of this launch is 232 MB
 // for that map: 38x).  0.152 vs 0.140 ms at cfg2, 0.287 vs 0.279 at 2000 ROIs (tools/bench_roi.py, same box): the re-fetches are
@@ -465,84 +538,18 @@ __global__ __launch_bounds__(256) void roi_align_fwd_rowsum2_kernel(const float*
     __shared__ int s_nrows;
     const int k = blockIdx.x, ph0 = blockIdx.y * 2, tid = threadIdx.x, NTH = blockDim.x;
     const bool two = ph0 + 1 < P;
-    const float* rec = rec_all + (size_t)k * roi_rec_words(P, H, W);
-    const float* wy0 = rec + ph0 * H;
-    const float* wy1 = wy0 + H;
-    const float* wx = rec + P * H;
-    const int* box = reinterpret_cast<const int*>(rec + (P + 1) * (H + W));
-    const int ylo = box[0], yhi = box[1], xlo = box[2], xhi = box[3];
-    const float inv_count = 1.0f / reinterpret_cast<const float*>(box)[4];
-    const float* __restrict__ fb = feat + (size_t)box[5] * H * W * C;
-    const int ncols = max(xhi - xlo + 1, 0);
-    if (tid == 0) {
-        int n = 0;
-        for (int y = ylo; y <= yhi; ++y) {
-            const float a = wy0[y], b = two ? wy1[y] : 0.0f;
-            if (a != 0.0f || b != 0.0f) { s_rows[n] = y * W; s_wa[n] = a * inv_count; s_wb[n] = b * inv_count; ++n; }
-        }
-        s_nrows = n;
+    const RoiRec R = roi_rec(rec_all, feat, k, C, H, W, P);
+    if (tid < 64) {      // wave 0
+        const int n = rs_row_list(R, ph0, two, H, W, tid, s_rows, s_wa, s_wb);
+        if (tid == 0) s_nrows = n;
     }
-    for (int e = tid; e < ncols * 8; e += NTH) {
-        const int xi = e >> 3, pw = e & 7;
-        s_wx[xi][pw] = pw < P ? wx[pw * W + xlo + xi] : 0.0f;
-    }
+    rs_fill_wx(s_wx, R, P, W, tid, NTH);
     __syncthreads();
     const int nrows = s_nrows;
     const int OC = MASKCAT ? 2 * C : C;
     for (int c = tid * 4; c < C; c += NTH * 4) {
-        const float* __restrict__ fc = fb + c;
         ga_f2 al[7], ah[7], bl[7], bh[7];
-#pragma unroll
-        for (int pw = 0; pw < 7; ++pw) al[pw] = ah[pw] = bl[pw] = bh[pw] = ga_f2{0.f, 0.f};
-        for (int xi = 0; xi < ncols; xi += 2) {
-            const bool pair = xi + 1 < ncols;            // wave-uniform; the odd last column is loaded twice, weight 0
-            const int x0 = (xlo + xi) * C, dx1 = pair ? C : 0;
-            ga_f2 ta0l = {0.f, 0.f}, ta0h = {0.f, 0.f}, ta1l = {0.f, 0.f}, ta1h = {0.f, 0.f};
-            ga_f2 tb0l = {0.f, 0.f}, tb0h = {0.f, 0.f}, tb1l = {0.f, 0.f}, tb1h = {0.f, 0.f};
-            int r = 0;
-            for (; r + 4 <= nrows; r += 4) {
-                float4 v0[4], v1[4];
-                float wa[4], wb[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float* src = fc + (size_t)s_rows[r + j] * C + x0;
-                    v0[j] = *reinterpret_cast<const float4*>(src);
-                    v1[j] = *reinterpret_cast<const float4*>(src + dx1);
-                    wa[j] = s_wa[r + j];
-                    wb[j] = s_wb[r + j];
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    ta0l = ga_fma(wa[j], ga_lo(v0[j]), ta0l); ta0h = ga_fma(wa[j], ga_hi(v0[j]), ta0h);
-                    ta1l = ga_fma(wa[j], ga_lo(v1[j]), ta1l); ta1h = ga_fma(wa[j], ga_hi(v1[j]), ta1h);
-                    tb0l = ga_fma(wb[j], ga_lo(v0[j]), tb0l); tb0h = ga_fma(wb[j], ga_hi(v0[j]), tb0h);
-                    tb1l = ga_fma(wb[j], ga_lo(v1[j]), tb1l); tb1h = ga_fma(wb[j], ga_hi(v1[j]), tb1h);
-                }
-            }
-            for (; r < nrows; ++r) {
-                const float* src = fc + (size_t)s_rows[r] * C + x0;
-                const float4 v0 = *reinterpret_cast<const float4*>(src);
-                const float4 v1 = *reinterpret_cast<const float4*>(src + dx1);
-                const float wa = s_wa[r], wb = s_wb[r];
-                ta0l = ga_fma(wa, ga_lo(v0), ta0l); ta0h = ga_fma(wa, ga_hi(v0), ta0h);
-                ta1l = ga_fma(wa, ga_lo(v1), ta1l); ta1h = ga_fma(wa, ga_hi(v1), ta1h);
-                tb0l = ga_fma(wb, ga_lo(v0), tb0l); tb0h = ga_fma(wb, ga_hi(v0), tb0h);
-                tb1l = ga_fma(wb, ga_lo(v1), tb1l); tb1h = ga_fma(wb, ga_hi(v1), tb1h);
-            }
-            const int xj = pair ? xi + 1 : xi;
-            const float4 wa0 = *reinterpret_cast<const float4*>(&s_wx[xi][0]), wb0 = *reinterpret_cast<const float4*>(&s_wx[xi][4]);
-            const float4 wa1 = *reinterpret_cast<const float4*>(&s_wx[xj][0]), wb1 = *reinterpret_cast<const float4*>(&s_wx[xj][4]);
-            const float m1 = pair ? 1.0f : 0.0f;
-            const float w0[7] = {wa0.x, wa0.y, wa0.z, wa0.w, wb0.x, wb0.y, wb0.z};
-            const float w1[7] = {m1 * wa1.x, m1 * wa1.y, m1 * wa1.z, m1 * wa1.w, m1 * wb1.x, m1 * wb1.y, m1 * wb1.z};
-#pragma unroll
-            for (int pw = 0; pw < 7; ++pw) {
-                al[pw] = ga_fma(w0[pw], ta0l, al[pw]); ah[pw] = ga_fma(w0[pw], ta0h, ah[pw]);
-                al[pw] = ga_fma(w1[pw], ta1l, al[pw]); ah[pw] = ga_fma(w1[pw], ta1h, ah[pw]);
-                bl[pw] = ga_fma(w0[pw], tb0l, bl[pw]); bh[pw] = ga_fma(w0[pw], tb0h, bh[pw]);
-                bl[pw] = ga_fma(w1[pw], tb1l, bl[pw]); bh[pw] = ga_fma(w1[pw], tb1h, bh[pw]);
-            }
-        }
+        rs_column_walk(s_rows, s_wa, s_wb, nrows, R.ncols, R.xlo, C, R.fb + c, s_wx, al, ah, bl, bh);
         typedef float ga_f4 __attribute__((ext_vector_type(4)));
 #pragma unroll
         for (int pw = 0; pw < 7; ++pw) {
@@ -572,72 +579,11 @@ __global__ __launch_bounds__(256) void roi_align_fwd_rowsum2_kernel(const float*
 // the mixed 4 + 3 Winograd tiling of csrc/winograd.hip).  `cat` never exists: the two-kernel path wrote its 401 MB (cfg2), read
 // them back in wino7_input_pair_kernel (0.288 ms) and wrote the 991 MB image; here the image is the only output.
 // Workgroup = (ROI r, 256-channel slice), four waves.  Phase A: wave w computes the bin rows 2w, 2w + 1 of the ROI for the lane's
-// 4 channels with the row-sum arithmetic of roi_align_fwd_rowsum2_kernel (the same operations in the same order: the values are
-// the bits that kernel writes) into an LDS patch [49][256].  Phase B: wave t transforms tile type t (36 / 30 / 30 / 25 positions)
-// of the patch - once as it is, once multiplied by the ROI's 7 x 7 mask - with the arithmetic of w7_input_tile and stores the
-// split (h, l) fp16 chunks (w7_store_pair's protocol: lane pairs exchange halves, 16 bytes per lane).  Rows r >= K (the pad up
+// 4 channels with the row-sum core of roi_align_fwd_rowsum2_kernel (the same functions: the values are the bits that kernel
+// writes) into an LDS patch [49][256].  Phase B: wave t transforms tile type t (36 / 30 / 30 / 25 positions)
+// of the patch - once as it is, once multiplied by the ROI's 7 x 7 mask - with w7_input_tile_regs of wino7_tile.h, the
+// transform and split (h, l) fp16 store of wino7_input_pair_kernel (lane pairs exchange halves, 16 bytes per lane).  Rows r >= K (the pad up
 // to a multiple of 32 rows the GEMM wants) are zero-filled.  The image is bit-identical to the two-kernel path's.
-#include "wino43_mats.h"
-namespace w7f {
-constexpr int NP[2] = {6, 5}, IN0[2] = {-1, 3}, QOFF[4] = {0, 36, 66, 96};
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ unsigned swap1(unsigned v) {
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false);      // quad_perm [1,0,3,2]
-}
-__device__ __forceinline__ void store_pair(float* p, const float4& v, float s) {         // (= w7_store_pair of winograd.hip)
-    unsigned h0, l0, h1, l1;
-    cim::pair_split2(v.x * s, v.y * s, h0, l0);
-    cim::pair_split2(v.z * s, v.w * s, h1, l1);
-    const bool odd = (threadIdx.x & 1) != 0;
-    const unsigned r0 = swap1(odd ? h0 : l0), r1 = swap1(odd ? h1 : l1);
-    const u4 o = odd ? u4{r0, r1, l0, l1} : u4{h0, h1, r0, r1};
-    __builtin_nontemporal_store(o, reinterpret_cast<u4*>(p));
-}
-__device__ __forceinline__ void fma4(float4& a, float s, const float4& v) {
-    a.x = fmaf(s, v.x, a.x); a.y = fmaf(s, v.y, a.y); a.z = fmaf(s, v.z, a.z); a.w = fmaf(s, v.w, a.w);
-}
-// one tile type of the patch: d = patch (x mask when MASKED) -> B^T d B -> pair image positions Q0 .. Q0 + NA NB
-template <int KA, int KB, bool MASKED>
-__device__ __forceinline__ void tile(const float4* __restrict__ patch, const float* __restrict__ mask49, float* __restrict__ V,
-                                     size_t MC, size_t off, const float* __restrict__ scale, int lane) {
-    constexpr int NA = NP[KA], NB = NP[KB], P = 7, Q0 = QOFF[KA * 2 + KB];
-    float4 d[NA][NB];
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-        const int iy = IN0[KA] + i;
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            const int ix = IN0[KB] + j;
-            if ((unsigned)iy < (unsigned)P && (unsigned)ix < (unsigned)P) {
-                d[i][j] = patch[(iy * P + ix) * 64 + lane];
-                if (MASKED) { const float m = mask49[iy * P + ix]; d[i][j] = make_float4(m * d[i][j].x, m * d[i][j].y, m * d[i][j].z, m * d[i][j].w); }
-            } else {
-                d[i][j] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-        float4 trow[NB];
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            trow[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int k = 0; k < NA; ++k)
-                if (W7_BT[KA][i][k] != 0.0f) fma4(trow[j], W7_BT[KA][i][k], d[k][j]);
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int k = 0; k < NB; ++k)
-                if (W7_BT[KB][j][k] != 0.0f) fma4(v, W7_BT[KB][j][k], trow[k]);
-            store_pair(V + (size_t)(Q0 + i * NB + j) * MC + off, v, scale[Q0 + i * NB + j]);
-        }
-    }
-}
-}  // namespace w7f
-
 __global__ __launch_bounds__(256) void roi_align_wino7_pair_kernel(const float* __restrict__ feat, const float* __restrict__ masks,
                                                                    float* __restrict__ V, int C, int H, int W, int K, int Rs,
                                                                    const float* __restrict__ rec_all,
@@ -655,105 +601,23 @@ __global__ __launch_bounds__(256) void roi_align_wino7_pair_kernel(const float* 
         if (c < C)
             for (int q = wave; q < 121; q += 4) {
                 float* dst = V + (size_t)q * MC + (size_t)r * C2 + c;
-                __builtin_nontemporal_store(w7f::u4{0, 0, 0, 0}, reinterpret_cast<w7f::u4*>(dst));
-                __builtin_nontemporal_store(w7f::u4{0, 0, 0, 0}, reinterpret_cast<w7f::u4*>(dst + C));
+                __builtin_nontemporal_store(w7_u4{0, 0, 0, 0}, reinterpret_cast<w7_u4*>(dst));
+                __builtin_nontemporal_store(w7_u4{0, 0, 0, 0}, reinterpret_cast<w7_u4*>(dst + C));
             }
         return;
     }
     const int k = r;
-    const float* rec = rec_all + (size_t)k * roi_rec_words(P, H, W);
-    const float* wx = rec + P * H;
-    const int* box = reinterpret_cast<const int*>(rec + (P + 1) * (H + W));
-    const int ylo = box[0], yhi = box[1], xlo = box[2], xhi = box[3];
-    const float inv_count = 1.0f / reinterpret_cast<const float*>(box)[4];
-    const float* __restrict__ fb = feat + (size_t)box[5] * H * W * C;
-    const int ncols = max(xhi - xlo + 1, 0);
-    // ---- phase A: bin rows ph0, ph0 + 1 of this wave (rowsum2's arithmetic)
+    const RoiRec R = roi_rec(rec_all, feat, k, C, H, W, P);
+    // ---- phase A: bin rows ph0, ph0 + 1 of this wave (the row-sum core: rowsum2's bits)
     const int ph0 = wave * 2;
     const bool two = ph0 + 1 < P;
-    const float* wy0 = rec + ph0 * H;
-    const float* wy1 = wy0 + H;
-    int nrows;
-    {
-        // the rows of the map with a non-zero weight in bin row ph0 or ph0 + 1, ascending (a wave-wide compaction of the loop
-        // rowsum2's thread 0 runs: same list, same order)
-        nrows = 0;
-        for (int y0 = ylo; y0 <= yhi; y0 += 64) {             // (an ROI spans up to RS_MAXD = 128 rows: two passes of the wave)
-            const int y = y0 + lane;
-            float a = 0.0f, b = 0.0f;
-            if (y <= yhi) { a = wy0[y]; b = two ? wy1[y] : 0.0f; }
-            const bool on = y <= yhi && (a != 0.0f || b != 0.0f);
-            const unsigned long long m = __ballot(on);
-            if (on) {
-                const int n = nrows + __popcll(m & ((1ull << lane) - 1ull));
-                s_rows[wave][n] = y * W; s_wa[wave][n] = a * inv_count; s_wb[wave][n] = b * inv_count;
-            }
-            nrows += __popcll(m);
-        }
-    }
-    for (int e = tid; e < ncols * 8; e += 256) {
-        const int xi = e >> 3, pw = e & 7;
-        s_wx[xi][pw] = pw < P ? wx[pw * W + xlo + xi] : 0.0f;
-    }
+    const int nrows = rs_row_list(R, ph0, two, H, W, lane, s_rows[wave], s_wa[wave], s_wb[wave]);
+    rs_fill_wx(s_wx, R, P, W, tid, 256);
     if (tid < 49) s_mask[tid] = masks[(size_t)k * 49 + tid];
     __syncthreads();
     if (c < C) {
-        const int* __restrict__ rows = s_rows[wave];
-        const float* __restrict__ rwa = s_wa[wave];
-        const float* __restrict__ rwb = s_wb[wave];
-        const float* __restrict__ fc = fb + c;
         ga_f2 al[7], ah[7], bl[7], bh[7];
-#pragma unroll
-        for (int pw = 0; pw < 7; ++pw) al[pw] = ah[pw] = bl[pw] = bh[pw] = ga_f2{0.f, 0.f};
-        for (int xi = 0; xi < ncols; xi += 2) {
-            const bool pair = xi + 1 < ncols;            // wave-uniform; the odd last column is loaded twice, weight 0
-            const int x0 = (xlo + xi) * C, dx1 = pair ? C : 0;
-            ga_f2 ta0l = {0.f, 0.f}, ta0h = {0.f, 0.f}, ta1l = {0.f, 0.f}, ta1h = {0.f, 0.f};
-            ga_f2 tb0l = {0.f, 0.f}, tb0h = {0.f, 0.f}, tb1l = {0.f, 0.f}, tb1h = {0.f, 0.f};
-            int rr = 0;
-            for (; rr + 4 <= nrows; rr += 4) {
-                float4 v0[4], v1[4];
-                float wa[4], wb[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float* src = fc + (size_t)rows[rr + j] * C + x0;
-                    v0[j] = *reinterpret_cast<const float4*>(src);
-                    v1[j] = *reinterpret_cast<const float4*>(src + dx1);
-                    wa[j] = rwa[rr + j];
-                    wb[j] = rwb[rr + j];
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    ta0l = ga_fma(wa[j], ga_lo(v0[j]), ta0l); ta0h = ga_fma(wa[j], ga_hi(v0[j]), ta0h);
-                    ta1l = ga_fma(wa[j], ga_lo(v1[j]), ta1l); ta1h = ga_fma(wa[j], ga_hi(v1[j]), ta1h);
-                    tb0l = ga_fma(wb[j], ga_lo(v0[j]), tb0l); tb0h = ga_fma(wb[j], ga_hi(v0[j]), tb0h);
-                    tb1l = ga_fma(wb[j], ga_lo(v1[j]), tb1l); tb1h = ga_fma(wb[j], ga_hi(v1[j]), tb1h);
-                }
-            }
-            for (; rr < nrows; ++rr) {
-                const float* src = fc + (size_t)rows[rr] * C + x0;
-                const float4 v0 = *reinterpret_cast<const float4*>(src);
-                const float4 v1 = *reinterpret_cast<const float4*>(src + dx1);
-                const float wa = rwa[rr], wb = rwb[rr];
-                ta0l = ga_fma(wa, ga_lo(v0), ta0l); ta0h = ga_fma(wa, ga_hi(v0), ta0h);
-                ta1l = ga_fma(wa, ga_lo(v1), ta1l); ta1h = ga_fma(wa, ga_hi(v1), ta1h);
-                tb0l = ga_fma(wb, ga_lo(v0), tb0l); tb0h = ga_fma(wb, ga_hi(v0), tb0h);
-                tb1l = ga_fma(wb, ga_lo(v1), tb1l); tb1h = ga_fma(wb, ga_hi(v1), tb1h);
-            }
-            const int xj = pair ? xi + 1 : xi;
-            const float4 wa0 = *reinterpret_cast<const float4*>(&s_wx[xi][0]), wb0 = *reinterpret_cast<const float4*>(&s_wx[xi][4]);
-            const float4 wa1 = *reinterpret_cast<const float4*>(&s_wx[xj][0]), wb1 = *reinterpret_cast<const float4*>(&s_wx[xj][4]);
-            const float m1 = pair ? 1.0f : 0.0f;
-            const float w0[7] = {wa0.x, wa0.y, wa0.z, wa0.w, wb0.x, wb0.y, wb0.z};
-            const float w1[7] = {m1 * wa1.x, m1 * wa1.y, m1 * wa1.z, m1 * wa1.w, m1 * wb1.x, m1 * wb1.y, m1 * wb1.z};
-#pragma unroll
-            for (int pw = 0; pw < 7; ++pw) {
-                al[pw] = ga_fma(w0[pw], ta0l, al[pw]); ah[pw] = ga_fma(w0[pw], ta0h, ah[pw]);
-                al[pw] = ga_fma(w1[pw], ta1l, al[pw]); ah[pw] = ga_fma(w1[pw], ta1h, ah[pw]);
-                bl[pw] = ga_fma(w0[pw], tb0l, bl[pw]); bh[pw] = ga_fma(w0[pw], tb0h, bh[pw]);
-                bl[pw] = ga_fma(w1[pw], tb1l, bl[pw]); bh[pw] = ga_fma(w1[pw], tb1h, bh[pw]);
-            }
-        }
+        rs_column_walk(s_rows[wave], s_wa[wave], s_wb[wave], nrows, R.ncols, R.xlo, C, R.fb + c, s_wx, al, ah, bl, bh);
 #pragma unroll
         for (int pw = 0; pw < 7; ++pw) {
             s_patch[(ph0 * P + pw) * 64 + lane] = make_float4(al[pw].x, al[pw].y, ah[pw].x, ah[pw].y);
@@ -764,11 +628,13 @@ __global__ __launch_bounds__(256) void roi_align_wino7_pair_kernel(const float* 
     // ---- phase B: tile type `wave` of the patch -> pair image, both halves of the channel concat
     if (c >= C) return;
     const size_t off = (size_t)r * C2 + c;
+    const auto plain = [&](int iy, int ix) { return s_patch[(iy * P + ix) * 64 + lane]; };
+    const auto masked = [&](int iy, int ix) { return vmul(s_mask[iy * P + ix], s_patch[(iy * P + ix) * 64 + lane]); };
     switch (wave) {
-        case 0: w7f::tile<0, 0, false>(s_patch, s_mask, V, MC, off, scale, lane); w7f::tile<0, 0, true>(s_patch, s_mask, V, MC, off + C, scale, lane); break;
-        case 1: w7f::tile<0, 1, false>(s_patch, s_mask, V, MC, off, scale, lane); w7f::tile<0, 1, true>(s_patch, s_mask, V, MC, off + C, scale, lane); break;
-        case 2: w7f::tile<1, 0, false>(s_patch, s_mask, V, MC, off, scale, lane); w7f::tile<1, 0, true>(s_patch, s_mask, V, MC, off + C, scale, lane); break;
-        default: w7f::tile<1, 1, false>(s_patch, s_mask, V, MC, off, scale, lane); w7f::tile<1, 1, true>(s_patch, s_mask, V, MC, off + C, scale, lane); break;
+        case 0: w7_input_tile_regs<0, 0>(plain, V, MC, off, scale); w7_input_tile_regs<0, 0>(masked, V, MC, off + C, scale); break;
+        case 1: w7_input_tile_regs<0, 1>(plain, V, MC, off, scale); w7_input_tile_regs<0, 1>(masked, V, MC, off + C, scale); break;
+        case 2: w7_input_tile_regs<1, 0>(plain, V, MC, off, scale); w7_input_tile_regs<1, 0>(masked, V, MC, off + C, scale); break;
+        default: w7_input_tile_regs<1, 1>(plain, V, MC, off, scale); w7_input_tile_regs<1, 1>(masked, V, MC, off + C, scale); break;
     }
 }
 
@@ -788,25 +654,11 @@ __global__ __launch_bounds__(256) void roi_align_wino7_pair_kernel(const float* 
 // Regions are dispatched centre first (they carry the most entries); groups meet in grad_in through atomicAdd.
 // ROIs per workgroup (template parameter GS): rg_group_size() below (32: 0.66, 96: 0.26, 160: 0.38, 256: 0.56 ms at 1000 ROIs).
 // Entry order inside a group: interleaved over the ROIs (see the entry map below); sub-blocks spread over the SIMDs.
-#ifndef CIM_ROI_RG_DIRECT
-#define CIM_ROI_RG_DIRECT 0         // 1 = no LDS staging: every wave loads its entries itself (L1 / L2 serve the re-reads)
-#endif
-#ifndef CIM_ROI_RG_EXP
-#define CIM_ROI_RG_EXP 0            // ablations: 1 = no consume phase, 2 = no gradient loads, 3 = records only
-#endif
 constexpr int RG_SBH = 3, RG_SBW = 4, RG_WR = 4, RG_WC = 4;
 constexpr int RG_RH = RG_SBH * RG_WR, RG_RW = RG_SBW * RG_WC;          // 12 x 16 pixels
 constexpr int RG_NT = 64 * RG_WR * RG_WC;                               // 1024 threads
-#ifndef CIM_ROI_RG_WIN
-#define CIM_ROI_RG_WIN 32
-#endif
-#ifndef CIM_ROI_RG_MAXE
-#define CIM_ROI_RG_MAXE 256
-#endif
-constexpr int RG_WIN = CIM_ROI_RG_WIN;                                  // entries per staging window (32; 16 = 64 lanes x one float4 per entry, 76 KB of LDS: two
-                                                                        // workgroups per CU instead of one - measured equal, 0.19 ms at cfg2, round 4)
-constexpr int RG_MAXE = CIM_ROI_RG_MAXE;                                // entries per super-window (records in LDS)
-static_assert(RG_WIN == 32 || RG_WIN == 16, "staging window: 32 or 16 entries");
+constexpr int RG_WIN = 32;                                              // entries per staging window
+constexpr int RG_MAXE = 256;                                            // entries per super-window (records in LDS)
 // ROIs per workgroup: 64, or 128 when 64 would make more than ~3.5 workgroups per CU (measured, ms at 64 / 128:
 // 1000 ROIs on 33 x 43: 0.188 / 0.284, 800 on 27 x 36: 0.159 / 0.253, 1200 on 41 x 54: 0.288 / 0.261, 2000 on 33 x 43: 0.353 / 0.321)
 static inline int rg_group_size(int K, int B, int C, int H, int W) {
@@ -941,10 +793,10 @@ __global__ __launch_bounds__(RG_NT) void roi_align_bwd_region_kernel(const float
         }
         __syncthreads();
     }
-    const int total = (CIM_ROI_RG_EXP == 6) ? 0 : d_base[RG_GS];
+    const int total = d_base[RG_GS];
 
     // loader role of this thread inside a staging window: entry le = tid / 32, two float4 of the slice's 64
-    const int le = RG_WIN == 32 ? tid >> 5 : tid >> 6, lq = RG_WIN == 32 ? (tid & 31) * 2 : (tid & 63);
+    const int le = tid >> 5, lq = (tid & 31) * 2;
     const int cbase = slice * 256;
     // consumer role: lane's 4 channels of the slice
     const int my_touch = (7 << (RG_SBH * wr)) | ((15 << (RG_SBW * wc)) << 16);
@@ -990,7 +842,7 @@ __global__ __launch_bounds__(RG_NT) void roi_align_bwd_region_kernel(const float
         }
         __syncthreads();
         const int n = min(RG_MAXE, total - w0);
-        const int nwin = (CIM_ROI_RG_EXP == 3 || CIM_ROI_RG_EXP == 5) ? 0 : (n + RG_WIN - 1) / RG_WIN;
+        const int nwin = (n + RG_WIN - 1) / RG_WIN;
         // ---- software pipeline over the staging windows: the next window's loads are in flight while this one is consumed
         // (two windows in flight - a second register set - measured no faster: 0.213 vs 0.207 ms)
         struct Regs { float4 r0, r1, h0, h1; float m; };
@@ -998,15 +850,15 @@ __global__ __launch_bounds__(RG_NT) void roi_align_bwd_region_kernel(const float
             const int e = win * RG_WIN + le;
             R.r0 = R.r1 = R.h0 = R.h1 = make_float4(0.f, 0.f, 0.f, 0.f);
             R.m = 0.0f;
-            if (e < n && CIM_ROI_RG_EXP != 2) {
+            if (e < n) {
                 const float* rr = erec + e * RG_REC;
                 const int off = reinterpret_cast<const int*>(rr)[0];
                 const int c0 = min(cbase + lq * 4, C - 4), c1 = min(cbase + lq * 4 + 4, C - 4);
                 R.r0 = *reinterpret_cast<const float4*>(grad_out + off + c0);
-                if (RG_WIN == 32) R.r1 = *reinterpret_cast<const float4*>(grad_out + off + c1);
+                R.r1 = *reinterpret_cast<const float4*>(grad_out + off + c1);
                 if (MASKCAT) {
                     R.h0 = *reinterpret_cast<const float4*>(grad_out + off + C + c0);
-                    if (RG_WIN == 32) R.h1 = *reinterpret_cast<const float4*>(grad_out + off + C + c1);
+                    R.h1 = *reinterpret_cast<const float4*>(grad_out + off + C + c1);
                     R.m = rr[1];
                 }
             }
@@ -1019,7 +871,7 @@ __global__ __launch_bounds__(RG_NT) void roi_align_bwd_region_kernel(const float
             }
             float* sb = &stage[buf][le][lq * 4];
             *reinterpret_cast<float4*>(sb) = a;
-            if (RG_WIN == 32) *reinterpret_cast<float4*>(sb + 4) = c;
+            *reinterpret_cast<float4*>(sb + 4) = c;
         };
         auto consume = [&](int buf, int win) {
             // entries of the window whose bin touches this wave's sub-block
@@ -1028,7 +880,6 @@ __global__ __launch_bounds__(RG_NT) void roi_align_bwd_region_kernel(const float
             if (lane < RG_WIN && e0 + lane < n) t = reinterpret_cast<const int*>(erec + (e0 + lane) * RG_REC)[2];
             const bool hit = ((t & my_touch & 0xffff) != 0) && (((t & my_touch) >> 16) != 0);
             unsigned long long todo = __ballot(hit);
-            if (CIM_ROI_RG_EXP == 1) todo = 0;
             while (todo) {
                 const int j = __ffsll((long long)todo) - 1;
                 todo &= todo - 1;
@@ -1052,69 +903,6 @@ __global__ __launch_bounds__(RG_NT) void roi_align_bwd_region_kernel(const float
                 }
             }
         };
-#if CIM_ROI_RG_DIRECT
-        // DIRECT variant: no LDS staging and no per-window barrier - every wave loads the gradient slices of the entries
-        // that touch its sub-block itself, four entries (8 x 16 B loads) in flight; the ~2.5 waves of the workgroup that
-        // share an entry re-read it from this CU's L1 / this XCD's L2 (all consumers of a region sit on one CU), so the
-        // fabric still sees each slice once per region.
-        (void)gload; (void)put; (void)consume; (void)nwin;
-        const float* __restrict__ gc = grad_out + min(cbase + lane * 4, C - 4);
-#define RD_LOAD(G, J)                                                                                  \
-        const float* rr##G = erec + (J) * RG_REC;                                                      \
-        const int off##G = reinterpret_cast<const int*>(rr##G)[0];                                     \
-        float4 G = *reinterpret_cast<const float4*>(gc + off##G);                                      \
-        float4 G##h;                                                                                   \
-        if (MASKCAT) G##h = *reinterpret_cast<const float4*>(gc + off##G + C);
-#define RD_ACC(G)                                                                                      \
-        {                                                                                              \
-            ga_f2 gl_ = ga_lo(G), gh_ = ga_hi(G);                                                      \
-            if (MASKCAT) {                                                                             \
-                const float m_ = rr##G[1];                                                             \
-                gl_ = ga_fma(m_, ga_lo(G##h), gl_);                                                    \
-                gh_ = ga_fma(m_, ga_hi(G##h), gh_);                                                    \
-            }                                                                                          \
-            const float4 wyq = *reinterpret_cast<const float4*>(rr##G + 4 + wr * 4);                   \
-            const float4 wxq = *reinterpret_cast<const float4*>(rr##G + 20 + wc * 4);                  \
-            const float wys[3] = {wyq.x, wyq.y, wyq.z};                                                \
-            const float wxs[4] = {wxq.x, wxq.y, wxq.z, wxq.w};                                         \
-            _Pragma("unroll") for (int i = 0; i < 3; ++i) {                                            \
-                const ga_f2 tl = ga_f2{wys[i], wys[i]} * gl_, th = ga_f2{wys[i], wys[i]} * gh_;        \
-                _Pragma("unroll") for (int jj = 0; jj < 4; ++jj) {                                     \
-                    accl[i * 4 + jj] = ga_fma(wxs[jj], tl, accl[i * 4 + jj]);                          \
-                    acch[i * 4 + jj] = ga_fma(wxs[jj], th, acch[i * 4 + jj]);                          \
-                }                                                                                      \
-            }                                                                                          \
-        }
-        for (int e0 = 0; e0 < n; e0 += 64) {
-            int t = 0;
-            if (e0 + lane < n) t = reinterpret_cast<const int*>(erec + (e0 + lane) * RG_REC)[2];
-            const bool hit = ((t & my_touch & 0xffff) != 0) && (((t & my_touch) >> 16) != 0);
-            unsigned long long todo = __ballot(hit);
-            while (todo) {
-                const int cnt = __popcll(todo);
-                if (cnt >= 4) {
-                    const int j0 = __ffsll((long long)todo) - 1; todo &= todo - 1;
-                    const int j1 = __ffsll((long long)todo) - 1; todo &= todo - 1;
-                    const int j2 = __ffsll((long long)todo) - 1; todo &= todo - 1;
-                    const int j3 = __ffsll((long long)todo) - 1; todo &= todo - 1;
-                    RD_LOAD(g0, e0 + j0)
-                    RD_LOAD(g1, e0 + j1)
-                    RD_LOAD(g2, e0 + j2)
-                    RD_LOAD(g3, e0 + j3)
-                    RD_ACC(g0)
-                    RD_ACC(g1)
-                    RD_ACC(g2)
-                    RD_ACC(g3)
-                } else {
-                    const int j0 = __ffsll((long long)todo) - 1; todo &= todo - 1;
-                    RD_LOAD(g0, e0 + j0)
-                    RD_ACC(g0)
-                }
-            }
-        }
-#undef RD_LOAD
-#undef RD_ACC
-#else
         Regs A;
         gload(A, 0);
         for (int win = 0; win < nwin; ++win) {
@@ -1123,11 +911,10 @@ __global__ __launch_bounds__(RG_NT) void roi_align_bwd_region_kernel(const float
             if (win + 1 < nwin) gload(A, win + 1);         // in flight while this window is consumed
             consume(win & 1, win);
         }
-#endif
     }
     // ---- flush this wave's 3 x 4 pixels
     const int cs = slice * 256 + lane * 4;
-    if (cs < C && (total > 0 || !use_atomic || partial) && ((CIM_ROI_RG_EXP != 4 && CIM_ROI_RG_EXP != 5 && CIM_ROI_RG_EXP != 6) || accl[0].x == 123.456f)) {
+    if (cs < C && (total > 0 || !use_atomic || partial)) {
 #pragma unroll
         for (int i = 0; i < RG_SBH; ++i)
 #pragma unroll
@@ -1142,7 +929,7 @@ __global__ __launch_bounds__(RG_NT) void roi_align_bwd_region_kernel(const float
                         __builtin_nontemporal_store(v.z, partial + (size_t)kgroup * B * H * W * C + o + 2);
                         __builtin_nontemporal_store(v.w, partial + (size_t)kgroup * B * H * W * C + o + 3);
                     } else if (use_atomic) {
-                        atomicAdd(dst + 0, v.x); atomicAdd(dst + 1, v.y); atomicAdd(dst + 2, v.z); atomicAdd(dst + 3, v.w);
+                        atomic_add_vec(dst, v);
                     } else {
                         *reinterpret_cast<float4*>(dst) = v;
                     }
@@ -1183,7 +970,7 @@ static RoiForms roi_forms(int B, int C, int H, int W, int K, int P, bool maskcat
 
 template <bool MASKCAT>
 int launch_fwd(const float* feat, const float* rois, const float* masks, float* out, int B, int C, int H, int W, int K,
-               int P, float scale, int sr, int aligned, hipStream_t st, float* ws = nullptr) {
+               int P, float scale, int sr, int aligned, hipStream_t st, float* ws) {
     if (K == 0) return 0;
     dim3 grid(K, P), block(256);
     const int form = roi_forms(B, C, H, W, K, P, MASKCAT, ws != nullptr, false).fwd;
@@ -1194,9 +981,8 @@ int launch_fwd(const float* feat, const float* rois, const float* masks, float* 
             hipLaunchKernelGGL((roi_align_fwd_rowsum2_kernel<MASKCAT>), dim3(K, (P + 1) / 2), dim3(nth), 0, st, feat, masks, out, C, H, W, P, ws);
             return 0;
         }
-        const int fz = (C >= 512 * CIM_ROI_FZ) ? CIM_ROI_FZ : 1;
-        hipLaunchKernelGGL((roi_align_fwd_agg_kernel<MASKCAT>), dim3(K, P, fz), dim3(fz > 1 ? 128 : 256), 0, st, feat, masks, out,
-                           C, H, W, P, ws, rois, scale, sr, aligned);
+        hipLaunchKernelGGL((roi_align_fwd_agg_kernel<MASKCAT>), grid, block, 0, st, feat, masks, out, C, H, W, P, ws, rois, scale, sr,
+                           aligned);
         return 0;
     }
     // sample-order kernel (the oracle's operation order: bit-identical; any C, P, map size)
@@ -1274,7 +1060,7 @@ static int launch_bwd_region(const float* go, const float* rois, const float* ma
 
 template <bool MASKCAT>
 int launch_bwd(const float* go, const float* rois, const float* masks, float* gin, int B, int C, int H, int W, int K,
-               int P, float scale, int sr, int aligned, float* ws, hipStream_t st, int tables_ready = 0, float* scratch = nullptr) {
+               int P, float scale, int sr, int aligned, float* ws, hipStream_t st, int tables_ready, float* scratch) {
     // region form (roi_forms).  With several ROI groups and no partial-map scratch the groups meet through atomicAdd: slow, but
     // every entry point works.
     const RoiForms f = roi_forms(B, C, H, W, K, P, MASKCAT, ws != nullptr, tables_ready != 0);
@@ -1297,32 +1083,95 @@ int launch_bwd(const float* go, const float* rois, const float* masks, float* gi
 
 }  // namespace
 
-#define ROI_ARGS_OK()                                                                     \
-    CIM_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && K >= 0 && P > 0 && P <= 65535);     \
-    CIM_CHECK_ARG(rois != nullptr || K == 0)
+// The body of the forward / backward C entry points: argument check, launch, launch error (`fn`: the entry, for the error text).
+#define ROI_CHECK_ARG(cond)                                                   \
+    do {                                                                      \
+        if (!(cond)) {                                                        \
+            cim::set_error("%s: bad argument: %s", fn, #cond);                \
+            return -1;                                                        \
+        }                                                                     \
+    } while (0)
+
+static int roi_finish(const char* fn, int rc) {
+    if (rc) return rc;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) cim::set_error("%s: %s", fn, hipGetErrorString(e));
+    return (int)e;
+}
+
+template <bool MASKCAT>
+static int run_fwd(const char* fn, const float* feat, const float* rois, const float* masks, float* out, int B, int C, int H, int W,
+                   int K, int P, float scale, int sr, int aligned, float* workspace, void* stream) {
+    ROI_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && K >= 0 && P > 0 && P <= 65535);
+    ROI_CHECK_ARG(rois != nullptr || K == 0);
+    ROI_CHECK_ARG(feat && ((out && (masks || !MASKCAT)) || K == 0));
+    return roi_finish(fn, launch_fwd<MASKCAT>(feat, rois, masks, out, B, C, H, W, K, P, scale, sr, aligned, cim::as_stream(stream), workspace));
+}
+
+template <bool MASKCAT>
+static int run_bwd(const char* fn, const float* grad_out, const float* rois, const float* masks, float* grad_in, int B, int C, int H,
+                   int W, int K, int P, float scale, int sr, int aligned, float* workspace, int tables_ready, float* scratch,
+                   void* stream) {
+    ROI_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && K >= 0 && P > 0 && P <= 65535);
+    ROI_CHECK_ARG(rois != nullptr || K == 0);
+    ROI_CHECK_ARG(grad_in && ((grad_out && (masks || !MASKCAT)) || K == 0) && (workspace || !tables_ready));
+    return roi_finish(fn, launch_bwd<MASKCAT>(grad_out, rois, masks, grad_in, B, C, H, W, K, P, scale, sr, aligned, workspace,
+                                              cim::as_stream(stream), tables_ready, scratch));
+}
 
 extern "C" int cim_roi_align_fwd(const float* feat, const float* rois, float* out, int B, int C, int H, int W, int K,
                                  int P, float spatial_scale, int sampling_ratio, int aligned, void* stream) {
-    ROI_ARGS_OK();
-    CIM_CHECK_ARG(feat && (out || K == 0));
-    int rc = launch_fwd<false>(feat, rois, nullptr, out, B, C, H, W, K, P, spatial_scale, sampling_ratio, aligned,
-                               cim::as_stream(stream));
-    if (rc) return rc;
-    CIM_CHECK_LAUNCH();
-    return 0;
+    return run_fwd<false>(__func__, feat, rois, nullptr, out, B, C, H, W, K, P, spatial_scale, sampling_ratio, aligned, nullptr, stream);
 }
 
 extern "C" int cim_roi_align_fwd_ws(const float* feat, const float* rois, float* out, int B, int C, int H, int W, int K,
                                     int P, float spatial_scale, int sampling_ratio, int aligned, float* workspace,
                                     void* stream) {
-    ROI_ARGS_OK();
-    CIM_CHECK_ARG(feat && (out || K == 0));
-    int rc = launch_fwd<false>(feat, rois, nullptr, out, B, C, H, W, K, P, spatial_scale, sampling_ratio, aligned,
-                               cim::as_stream(stream), workspace);
-    if (rc) return rc;
-    CIM_CHECK_LAUNCH();
-    return 0;
+    return run_fwd<false>(__func__, feat, rois, nullptr, out, B, C, H, W, K, P, spatial_scale, sampling_ratio, aligned, workspace, stream);
 }
+
+extern "C" int cim_roi_align_maskcat_fwd(const float* feat, const float* rois, const float* masks, float* cat, int B,
+                                         int C, int H, int W, int K, int P, float spatial_scale, int sampling_ratio,
+                                         int aligned, void* stream) {
+    return run_fwd<true>(__func__, feat, rois, masks, cat, B, C, H, W, K, P, spatial_scale, sampling_ratio, aligned, nullptr, stream);
+}
+
+extern "C" int cim_roi_align_maskcat_fwd_ws(const float* feat, const float* rois, const float* masks, float* cat, int B,
+                                            int C, int H, int W, int K, int P, float spatial_scale, int sampling_ratio,
+                                            int aligned, float* workspace, void* stream) {
+    return run_fwd<true>(__func__, feat, rois, masks, cat, B, C, H, W, K, P, spatial_scale, sampling_ratio, aligned, workspace, stream);
+}
+
+// (without tables_ready / scratch: the tables are rebuilt, and several ROI groups meet through atomicAdd)
+extern "C" int cim_roi_align_bwd(const float* grad_out, const float* rois, float* grad_in, int B, int C, int H, int W,
+                                 int K, int P, float spatial_scale, int sampling_ratio, int aligned, float* workspace,
+                                 void* stream) {
+    return run_bwd<false>(__func__, grad_out, rois, nullptr, grad_in, B, C, H, W, K, P, spatial_scale, sampling_ratio, aligned, workspace,
+                          0, nullptr, stream);
+}
+
+extern "C" int cim_roi_align_bwd_ws(const float* grad_out, const float* rois, float* grad_in, int B, int C, int H, int W,
+                                    int K, int P, float spatial_scale, int sampling_ratio, int aligned, float* workspace,
+                                    int tables_ready, float* scratch, void* stream) {
+    return run_bwd<false>(__func__, grad_out, rois, nullptr, grad_in, B, C, H, W, K, P, spatial_scale, sampling_ratio, aligned, workspace,
+                          tables_ready, scratch, stream);
+}
+
+extern "C" int cim_roi_align_maskcat_bwd(const float* grad_cat, const float* rois, const float* masks, float* grad_in,
+                                         int B, int C, int H, int W, int K, int P, float spatial_scale,
+                                         int sampling_ratio, int aligned, float* workspace, void* stream) {
+    return run_bwd<true>(__func__, grad_cat, rois, masks, grad_in, B, C, H, W, K, P, spatial_scale, sampling_ratio, aligned, workspace,
+                         0, nullptr, stream);
+}
+
+extern "C" int cim_roi_align_maskcat_bwd_ws(const float* grad_cat, const float* rois, const float* masks, float* grad_in,
+                                            int B, int C, int H, int W, int K, int P, float spatial_scale,
+                                            int sampling_ratio, int aligned, float* workspace, int tables_ready,
+                                            float* scratch, void* stream) {
+    return run_bwd<true>(__func__, grad_cat, rois, masks, grad_in, B, C, H, W, K, P, spatial_scale, sampling_ratio, aligned, workspace,
+                         tables_ready, scratch, stream);
+}
+#undef ROI_CHECK_ARG
 
 extern "C" int cim_roi_align_wino7_pair_fwd(const float* feat, const float* rois, const float* masks, void* V, const float* scale,
                                            int B, int C, int H, int W, int K, int Rs, int P, float spatial_scale,
@@ -1335,18 +1184,6 @@ extern "C" int cim_roi_align_wino7_pair_fwd(const float* feat, const float* rois
                        spatial_scale, sampling_ratio, aligned);
     hipLaunchKernelGGL(roi_align_wino7_pair_kernel, dim3((unsigned)Rs, (unsigned)((C + 255) / 256)), dim3(256), 0, st, feat, masks,
                        (float*)V, C, H, W, K, Rs, workspace, scale);
-    CIM_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int cim_roi_align_maskcat_fwd_ws(const float* feat, const float* rois, const float* masks, float* cat, int B,
-                                            int C, int H, int W, int K, int P, float spatial_scale, int sampling_ratio,
-                                            int aligned, float* workspace, void* stream) {
-    ROI_ARGS_OK();
-    CIM_CHECK_ARG(feat && ((cat && masks) || K == 0));
-    int rc = launch_fwd<true>(feat, rois, masks, cat, B, C, H, W, K, P, spatial_scale, sampling_ratio, aligned,
-                              cim::as_stream(stream), workspace);
-    if (rc) return rc;
     CIM_CHECK_LAUNCH();
     return 0;
 }
@@ -1366,69 +1203,8 @@ extern "C" long long cim_roi_align_bwd_workspace(int K, int P, int H, int W) {
     return (long long)sizeof(float) * (long long)K * roi_rec_words(P, H, W);
 }
 
-extern "C" int cim_roi_align_bwd(const float* grad_out, const float* rois, float* grad_in, int B, int C, int H, int W,
-                                 int K, int P, float spatial_scale, int sampling_ratio, int aligned, float* workspace,
-                                 void* stream) {
-    ROI_ARGS_OK();
-    CIM_CHECK_ARG(grad_in && (grad_out || K == 0));
-    int rc = launch_bwd<false>(grad_out, rois, nullptr, grad_in, B, C, H, W, K, P, spatial_scale, sampling_ratio,
-                               aligned, workspace, cim::as_stream(stream));
-    if (rc) return rc;
-    CIM_CHECK_LAUNCH();
-    return 0;
-}
-
 extern "C" long long cim_roi_align_bwd_scratch(int K, int B, int C, int H, int W) {
     const int GS = rg_group_size(K, B, C, H, W);
     const long long groups = (K + GS - 1) / GS;
     return groups > 1 ? (long long)sizeof(float) * groups * B * H * W * C : 0;
-}
-
-extern "C" int cim_roi_align_bwd_ws(const float* grad_out, const float* rois, float* grad_in, int B, int C, int H, int W,
-                                    int K, int P, float spatial_scale, int sampling_ratio, int aligned, float* workspace,
-                                    int tables_ready, float* scratch, void* stream) {
-    ROI_ARGS_OK();
-    CIM_CHECK_ARG(grad_in && (grad_out || K == 0) && (workspace || !tables_ready));
-    int rc = launch_bwd<false>(grad_out, rois, nullptr, grad_in, B, C, H, W, K, P, spatial_scale, sampling_ratio,
-                               aligned, workspace, cim::as_stream(stream), tables_ready, scratch);
-    if (rc) return rc;
-    CIM_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int cim_roi_align_maskcat_bwd_ws(const float* grad_cat, const float* rois, const float* masks, float* grad_in,
-                                            int B, int C, int H, int W, int K, int P, float spatial_scale,
-                                            int sampling_ratio, int aligned, float* workspace, int tables_ready,
-                                            float* scratch, void* stream) {
-    ROI_ARGS_OK();
-    CIM_CHECK_ARG(grad_in && ((grad_cat && masks) || K == 0) && (workspace || !tables_ready));
-    int rc = launch_bwd<true>(grad_cat, rois, masks, grad_in, B, C, H, W, K, P, spatial_scale, sampling_ratio, aligned,
-                              workspace, cim::as_stream(stream), tables_ready, scratch);
-    if (rc) return rc;
-    CIM_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int cim_roi_align_maskcat_fwd(const float* feat, const float* rois, const float* masks, float* cat, int B,
-                                         int C, int H, int W, int K, int P, float spatial_scale, int sampling_ratio,
-                                         int aligned, void* stream) {
-    ROI_ARGS_OK();
-    CIM_CHECK_ARG(feat && ((cat && masks) || K == 0));
-    int rc = launch_fwd<true>(feat, rois, masks, cat, B, C, H, W, K, P, spatial_scale, sampling_ratio, aligned,
-                              cim::as_stream(stream));
-    if (rc) return rc;
-    CIM_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int cim_roi_align_maskcat_bwd(const float* grad_cat, const float* rois, const float* masks, float* grad_in,
-                                         int B, int C, int H, int W, int K, int P, float spatial_scale,
-                                         int sampling_ratio, int aligned, float* workspace, void* stream) {
-    ROI_ARGS_OK();
-    CIM_CHECK_ARG(grad_in && ((grad_cat && masks) || K == 0));
-    int rc = launch_bwd<true>(grad_cat, rois, masks, grad_in, B, C, H, W, K, P, spatial_scale, sampling_ratio, aligned,
-                              workspace, cim::as_stream(stream));
-    if (rc) return rc;
-    CIM_CHECK_LAUNCH();
-    return 0;
 }

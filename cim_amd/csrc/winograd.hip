@@ -12,16 +12,13 @@
 // infrastructure (experiments/csrc/winograd_all.hip, round 5).
 #include "common.h"
 #include "../../include/cim_hip.h"
-#include "wino43_mats.h"
+#include "wino7_tile.h"
 
 namespace {
 
 __device__ __forceinline__ float4 f4(float v) { return make_float4(v, v, v, v); }
 __device__ __forceinline__ float2 f2(float v) { return make_float2(v, v); }
 __device__ __forceinline__ void fma2(float2& a, float s, float2 v) { a.x = fmaf(s, v.x, a.x); a.y = fmaf(s, v.y, a.y); }
-__device__ __forceinline__ void fma4(float4& a, float s, float4 v) {
-    a.x = fmaf(s, v.x, a.x); a.y = fmaf(s, v.y, a.y); a.z = fmaf(s, v.z, a.z); a.w = fmaf(s, v.w, a.w);
-}
 
 // =============================================================================================
 // Mixed tiling of the 7 x 7 ROI map: one 4-wide and one 3-wide tile per axis (4 + 3 = 7) instead of two 4-wide tiles
@@ -58,24 +55,7 @@ __device__ __forceinline__ void w7_store(float* p, float4 v) {
 #endif
 }
 
-// ---- pair-image output (f16x2p GEMM engine, gemm_pair.hip) ------------------------------------------------------------
-// A lane holds 4 consecutive channels c .. c+3 (c = 4 x its index along C), its neighbour (lane ^ 1) the other half of the
-// 8-channel chunk [h: 8 x f16 | l: 8 x f16].  The even lane hands its two l words to the odd lane and receives the odd lane's
-// two h words (one quad_perm DPP move each way), so both store 16 contiguous bytes - the even lane the h half, the odd lane
-// the l half - at the byte offset the fp32 float4 would have gone to: pair images keep the fp32 tensor's addressing.
-typedef unsigned w7_u4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ unsigned w7_swap1(unsigned v) {
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false);      // quad_perm [1,0,3,2]
-}
-__device__ __forceinline__ void w7_store_pair(float* p, const float4& v, float s) {
-    unsigned h0, l0, h1, l1;
-    cim::pair_split2(v.x * s, v.y * s, h0, l0);
-    cim::pair_split2(v.z * s, v.w * s, h1, l1);
-    const bool odd = (threadIdx.x & 1) != 0;
-    const unsigned r0 = w7_swap1(odd ? h0 : l0), r1 = w7_swap1(odd ? h1 : l1);
-    const w7_u4 o = odd ? w7_u4{r0, r1, l0, l1} : w7_u4{h0, h1, r0, r1};
-    __builtin_nontemporal_store(o, reinterpret_cast<w7_u4*>(p));
-}
+// pair-image output: w7_store_pair of wino7_tile.h
 __device__ __forceinline__ void w7_store_pair(float*, const float2&, float) {}      // (only 4-channel lanes write pair images)
 __device__ __forceinline__ void w7_store_pair(float*, float, float) {}
 
@@ -132,63 +112,26 @@ template <typename T> __device__ __forceinline__ T vload_once(const float* p) {
 #endif
 }
 
-struct W7 {
-    static constexpr int NP[2] = {6, 5};      // positions per axis
-    static constexpr int OUT[2] = {4, 3};     // outputs per axis
-    static constexpr int IN0[2] = {-1, 3};    // first input row / column of the tile's patch
-    static constexpr int OUT0[2] = {0, 4};    // first output row / column
-    static constexpr int QOFF[4] = {0, 36, 66, 96};   // first position of tile type ka * 2 + kb (121 in total)
-};
-
 __host__ __device__ constexpr float w7_abs_row_sum(const float (&M)[6], int n) {
     float s = 0.0f;
     for (int k = 0; k < n; ++k) s += M[k] < 0 ? -M[k] : M[k];
     return s;
 }
 
-template <int KA, int KB, bool AMAX, int VW, bool PAIR = false>
+// x [R][7][7][C] fp32 -> tile type (KA, KB) of the pair image V [121][R (position stride, padded)][C], scale [121]
+template <int KA, int KB, bool AMAX>
 __device__ __forceinline__ void w7_input_tile(const float* __restrict__ x, float* __restrict__ V, int r, int R, int C,
-                                              unsigned* __restrict__ row_amax, const float* __restrict__ scale = nullptr) {
-    // PAIR: V is a pair image [121][R (position stride, padded)][C], scale [121]; x rows are indexed by r as before
+                                              unsigned* __restrict__ row_amax, const float* __restrict__ scale) {
     constexpr int NA = W7::NP[KA], NB = W7::NP[KB], P = 7, Q0 = W7::QOFF[KA * 2 + KB];
-    typedef typename w7_vec<VW>::T VT;
-    const size_t MC = (size_t)R * C;
     float dmax = 0.0f;
-    for (int c = threadIdx.x * VW; c < C; c += 256 * VW) {
-        VT d[NA][NB];
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            const int iy = W7::IN0[KA] + i;
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                const int ix = W7::IN0[KB] + j;
-                if ((unsigned)iy < (unsigned)P && (unsigned)ix < (unsigned)P) d[i][j] = vload<VT>(x + (((size_t)r * P + iy) * P + ix) * C + c);
-                else vzero(d[i][j]);
-                if constexpr (AMAX) dmax = fmaxf(dmax, vamax(d[i][j]));
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            VT trow[NB];
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                vzero(trow[j]);
-#pragma unroll
-                for (int k = 0; k < NA; ++k)
-                    if (W7_BT[KA][i][k] != 0.0f) vfma(trow[j], W7_BT[KA][i][k], d[k][j]);
-            }
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                VT v;
-                vzero(v);
-#pragma unroll
-                for (int k = 0; k < NB; ++k)
-                    if (W7_BT[KB][j][k] != 0.0f) vfma(v, W7_BT[KB][j][k], trow[k]);
-                if constexpr (PAIR) w7_store_pair(V + (size_t)(Q0 + i * NB + j) * MC + (size_t)r * C + c, v, scale[Q0 + i * NB + j]);
-                else w7_store(V + (size_t)(Q0 + i * NB + j) * MC + (size_t)r * C + c, v);
-            }
-        }
-    }
+    for (int c = threadIdx.x * 4; c < C; c += 256 * 4)
+        w7_input_tile_regs<KA, KB>(
+            [&](int iy, int ix) {
+                const float4 v = vload<float4>(x + (((size_t)r * P + iy) * P + ix) * C + c);
+                if constexpr (AMAX) dmax = fmaxf(dmax, vamax(v));
+                return v;
+            },
+            V, (size_t)R * C, (size_t)r * C + c, scale);
     if constexpr (AMAX) {       // row-scale bounds of this tile's positions (see wino43_input_kernel)
         __shared__ float red[4];
 #pragma unroll
@@ -225,10 +168,10 @@ __global__ __launch_bounds__(256) void wino7_input_pair_kernel(const float* __re
         return;
     }
     switch (blockIdx.y) {
-        case 0: w7_input_tile<0, 0, false, 4, true>(x, V, r, Rs, C, nullptr, scale); break;
-        case 1: w7_input_tile<0, 1, false, 4, true>(x, V, r, Rs, C, nullptr, scale); break;
-        case 2: w7_input_tile<1, 0, false, 4, true>(x, V, r, Rs, C, nullptr, scale); break;
-        default: w7_input_tile<1, 1, false, 4, true>(x, V, r, Rs, C, nullptr, scale); break;
+        case 0: w7_input_tile<0, 0, false>(x, V, r, Rs, C, nullptr, scale); break;
+        case 1: w7_input_tile<0, 1, false>(x, V, r, Rs, C, nullptr, scale); break;
+        case 2: w7_input_tile<1, 0, false>(x, V, r, Rs, C, nullptr, scale); break;
+        default: w7_input_tile<1, 1, false>(x, V, r, Rs, C, nullptr, scale); break;
     }
 }
 
