@@ -40,20 +40,15 @@ using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
 typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
 
-#ifndef CIM_RING_SCHED
-#define CIM_RING_SCHED 1
-#endif
-#ifndef CIM_RING_PRODUCER
-#define CIM_RING_PRODUCER 0     // 1: a fifth wave issues every LDS-DMA instruction of the workgroup, the four others hold MFMAs and fragment
-#endif                          // reads only.  FASTER ALONE (0.46-0.47 against 0.42-0.43 of the f16 peak: the 256 x 256 kernel's rate) and
-                                // SLOWER WHERE IT IS USED: beside the backbone's backward the last phase takes 3.69 ms with it, 3.60 without
-                                // (the chains' kernels get less of the CU: profiles/r6/gemm_pair_ring_kernel.txt) - not the product's build
-#ifndef CIM_RING_DBG
-#define CIM_RING_DBG 0
-#endif
+// Ablation builds, never the product's (tools/build_alt.sh expN gemm_pair.hip -DCIM_PAIR_EXP=N; the tables of profiles/rN and
+// tools/bench_gemm_pair.py): what gemm_pair_kernel's slab loop costs without its LDS-DMA (3), without its fragment reads = MFMA only
+// (4), without both (5).  Each constant is tested once, where the loop issues / reads.
 #ifndef CIM_PAIR_EXP
-#define CIM_PAIR_EXP 0          // ablation switches (tools/bench_gemm_pair.py); 0 = product
+#define CIM_PAIR_EXP 0
 #endif
+static_assert(CIM_PAIR_EXP == 0 || (CIM_PAIR_EXP >= 3 && CIM_PAIR_EXP <= 5), "CIM_PAIR_EXP: 0 (product), 3, 4 or 5");
+constexpr bool ABL_NO_LOOP_DMA = CIM_PAIR_EXP == 3 || CIM_PAIR_EXP == 5;
+constexpr bool ABL_NO_LOOP_READS = CIM_PAIR_EXP == 4 || CIM_PAIR_EXP == 5;
 
 // Two kernels (wave tile 128 x 64 in both, four waves along N):
 //   gemm_pair_kernel: 256 x 256 tiles, eight waves = two per SIMD at <= 256 registers, two 64 KB slabs of 32 k in LDS: the workgroup OWNS
@@ -71,7 +66,7 @@ constexpr int OPER = 256 * BK * 4;        // 32768 B per operand and slab
 constexpr int SLAB = 2 * OPER;
 constexpr int LDS_BYTES = 2 * SLAB;       // 131072
 // the ring kernel
-constexpr int RBM = 128, RBK = 16, RNT = 256 + 64 * CIM_RING_PRODUCER, RSTAGES = 5;
+constexpr int RBM = 128, RBK = 16, RNT = 256, RSTAGES = 5;
 constexpr int RSTAGE_A = RBM * RBK * 4, RSTAGE_B = BN * RBK * 4, RSTAGE = RSTAGE_A + RSTAGE_B;      // 8 KB + 16 KB
 constexpr int RIPA = RSTAGE_A / 1024 / 4, RIPB = RSTAGE_B / 1024 / 4;                                // LDS-DMA instructions per wave and slab: 2 + 4
 constexpr int RLDS_BYTES = RSTAGES * RSTAGE;      // 122880
@@ -146,57 +141,13 @@ __device__ __forceinline__ void glds16x2(const char* sbase, unsigned o0, unsigne
 __device__ __forceinline__ unsigned lds_addr(const char* p) { return (unsigned)(size_t)(lds_ptr_t)p; }
 
 // ---- staging ---------------------------------------------------------------------------------------
-// KC: instruction i (0..31) covers tile rows 8i .. 8i+7 = double rows 4i .. 4i+3; a wave issues i = 4w .. 4w+3.
-// LDS position (double row d, slot s) holds global (row 2d + (s >> 3), chunk (s & 7) ^ (d & 7)); chunk p = 2 * kgroup + plane.
-template <int W, int IPW, int KROWS = BK>
-struct StageKC {
-    unsigned off[IPW];    // byte offsets of this lane's source chunks relative to (base + k0 * 4)
-    __device__ __forceinline__ void init(int row0, int rows, int ld, int wave, int lane) {
-#pragma unroll
-        for (int ii = 0; ii < IPW; ++ii) {
-            const int d = 4 * (wave * IPW + ii) + (lane >> 4);
-            const int s = lane & 15;
-            const int r = min(row0 + 2 * d + (s >> 3), rows - 1);
-            const int p = (s & 7) ^ (d & 7);
-            off[ii] = (unsigned)r * (unsigned)ld * 4u + (unsigned)p * 16u;
-        }
-    }
+// A wave's share of one operand's slab: IPW LDS-DMA instructions (1 KiB of LDS each) from per-lane source offsets that the layout's
+// init() computes once.  Two go out as one asm statement, more as groups of four (a 4-wide group built from two 2-wide ones would
+// put a second M0 save / restore pair into the loop).
+template <int IPW>
+struct StageOffsets {
+    unsigned off[IPW];    // byte offsets of this lane's source chunks relative to the operand's base at the slab's first k
     __device__ __forceinline__ void issue(const char* base_k, const char* lds_oper, int wave) const {
-#pragma unroll
-        for (int q = 0; q < IPW; q += 4)
-            glds16x4(base_k, off[q], off[q + 1], off[q + 2], off[q + 3], lds_addr(lds_oper) + (wave * IPW + q) * 1024);
-    }
-    static __device__ __forceinline__ size_t k_step_bytes(int) { return (size_t)BK * 4; }
-};
-// MC, W = 256 tile columns: instruction i = k row i of the slab (1024 B); lane q loads chunk q ^ swz(k),
-// swz(k) = (k & 1) | ((k >> 1) & 1) << 3 (k & 3 = ii for k = 4w + ii).  W = 128 (a k row = 512 B = 32 chunks): instruction i = k rows
-// 2i and 2i + 1, lane q loads chunk (q & 31) ^ swz(k) of row k = 2i + (q >> 5) - the same LDS image at a row pitch of 512 B.
-template <int W, int IPW, int KROWS = BK>
-struct StageMC {
-    unsigned off[IPW];
-    __device__ __forceinline__ void init(int col0, int cols, int ld, int wave, int lane) {
-        const int maxchunk = ((cols - col0) * 4 - 16) / 16;       // last whole chunk of the row that belongs to the matrix
-#pragma unroll
-        for (int ii = 0; ii < IPW; ++ii) {
-            if constexpr (W == 256) {
-                const int swz = (ii & 1) | (((ii >> 1) & 1) << 3);    // (k & 3 = ii & 3 for k = IPW w + ii)
-                const int c = min(lane ^ swz, maxchunk);
-                off[ii] = (unsigned)(wave * IPW + ii) * (unsigned)ld * 4u + (unsigned)col0 * 4u + (unsigned)c * 16u;
-            } else {
-                const int k = 2 * (wave * IPW + ii) + (lane >> 5);
-                const int swz = (lane >> 5) | ((ii & 1) << 3);        // (k & 1, (k >> 1) & 1 = ii & 1: IPW is even)
-                const int c = min((lane & 31) ^ swz, maxchunk);
-                off[ii] = (unsigned)k * (unsigned)ld * 4u + (unsigned)col0 * 4u + (unsigned)c * 16u;
-            }
-        }
-    }
-    __device__ __forceinline__ void issue(const char* base_k, const char* lds_oper, int wave) const {
-#if CIM_RING_DBG == 2 || CIM_RING_DBG == 4 || CIM_RING_DBG == 6
-        if constexpr (W == 128) return;
-#endif
-#if CIM_RING_DBG == 3 || CIM_RING_DBG == 4 || CIM_RING_DBG == 6
-        if constexpr (KROWS == 16 && W == 256) return;
-#endif
         if constexpr (IPW == 2) {
             glds16x2(base_k, off[0], off[1], lds_addr(lds_oper) + (wave * IPW) * 1024);
         } else {
@@ -207,10 +158,45 @@ struct StageMC {
     }
     // instructions 2h, 2h + 1 of this wave's IPW
     __device__ __forceinline__ void issue_pair(const char* base_k, const char* lds_oper, int wave, int h) const {
-#if CIM_RING_DBG == 3 || CIM_RING_DBG == 4 || CIM_RING_DBG == 6
-        if constexpr (KROWS == 16 && W == 256) return;
-#endif
         glds16x2(base_k, off[2 * h], off[2 * h + 1], lds_addr(lds_oper) + (wave * IPW + 2 * h) * 1024);
+    }
+};
+// KC: instruction i (0..31) covers tile rows 8i .. 8i+7 = double rows 4i .. 4i+3; a wave issues i = 4w .. 4w+3.
+// LDS position (double row d, slot s) holds global (row 2d + (s >> 3), chunk (s & 7) ^ (d & 7)); chunk p = 2 * kgroup + plane.
+template <int W, int IPW, int KROWS = BK>
+struct StageKC : StageOffsets<IPW> {
+    __device__ __forceinline__ void init(int row0, int rows, int ld, int wave, int lane) {
+#pragma unroll
+        for (int ii = 0; ii < IPW; ++ii) {
+            const int d = 4 * (wave * IPW + ii) + (lane >> 4);
+            const int s = lane & 15;
+            const int r = min(row0 + 2 * d + (s >> 3), rows - 1);
+            const int p = (s & 7) ^ (d & 7);
+            this->off[ii] = (unsigned)r * (unsigned)ld * 4u + (unsigned)p * 16u;
+        }
+    }
+    static __device__ __forceinline__ size_t k_step_bytes(int) { return (size_t)BK * 4; }
+};
+// MC, W = 256 tile columns: instruction i = k row i of the slab (1024 B); lane q loads chunk q ^ swz(k),
+// swz(k) = (k & 1) | ((k >> 1) & 1) << 3 (k & 3 = ii for k = 4w + ii).  W = 128 (a k row = 512 B = 32 chunks): instruction i = k rows
+// 2i and 2i + 1, lane q loads chunk (q & 31) ^ swz(k) of row k = 2i + (q >> 5) - the same LDS image at a row pitch of 512 B.
+template <int W, int IPW, int KROWS = BK>
+struct StageMC : StageOffsets<IPW> {
+    __device__ __forceinline__ void init(int col0, int cols, int ld, int wave, int lane) {
+        const int maxchunk = ((cols - col0) * 4 - 16) / 16;       // last whole chunk of the row that belongs to the matrix
+#pragma unroll
+        for (int ii = 0; ii < IPW; ++ii) {
+            if constexpr (W == 256) {
+                const int swz = (ii & 1) | (((ii >> 1) & 1) << 3);    // (k & 3 = ii & 3 for k = IPW w + ii)
+                const int c = min(lane ^ swz, maxchunk);
+                this->off[ii] = (unsigned)(wave * IPW + ii) * (unsigned)ld * 4u + (unsigned)col0 * 4u + (unsigned)c * 16u;
+            } else {
+                const int k = 2 * (wave * IPW + ii) + (lane >> 5);
+                const int swz = (lane >> 5) | ((ii & 1) << 3);        // (k & 1, (k >> 1) & 1 = ii & 1: IPW is even)
+                const int c = min((lane & 31) ^ swz, maxchunk);
+                this->off[ii] = (unsigned)k * (unsigned)ld * 4u + (unsigned)col0 * 4u + (unsigned)c * 16u;
+            }
+        }
     }
     static __device__ __forceinline__ size_t k_step_bytes(int ld) { return (size_t)KROWS * ld * 4; }
 };
@@ -304,9 +290,122 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
     return v;
 }
 
-template <int TBM>
-__device__ __forceinline__ void pair_epilogue(const PairArgs& g, f32x16 (&acc)[MI][NI], float (&bvj)[NI], float* Cb, int zsplit, int zb,
-                                              int m0, int n0, int wm, int wn, int lane) {
+__device__ __forceinline__ unsigned abs_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
+__device__ __forceinline__ unsigned abs_bits(unsigned x) { return x & 0x7fffffffu; }
+// max |x| over the four elements of a float4 (or of a uint4 of float bit patterns), as a bit pattern
+template <class V4>
+__device__ __forceinline__ unsigned abs_bits_max4(const V4& v) {
+    return max(max(abs_bits(v.x), abs_bits(v.y)), max(abs_bits(v.z), abs_bits(v.w)));
+}
+
+// The maximum of `v` over a workgroup of 256 threads goes into *word with ONE atomicMax per workgroup (through LDS), not one per
+// wave: the ~2000 waves that are resident when a launch starts all see a zero word and fire on one address at ~12 ns each in L2 (round
+// 6: 54-77 us of the fc1 forward's split-K reduce, 65 / 35 us of the step's two masked-stats launches; 13 us without).  Every thread
+// of the workgroup calls it; what a caller wrote to LDS before the call is visible to the whole workgroup behind it (its one barrier).
+__device__ __forceinline__ void block_amax_publish(unsigned* word, unsigned v) {
+    __shared__ unsigned s_m[4];
+    v = wave_max_u32(v);
+    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) cim::amax_publish(word, max(max(s_m[0], s_m[1]), max(s_m[2], s_m[3])));
+}
+
+// ---- what the two GEMM kernels share ------------------------------------------------------------------
+// A workgroup's place in the product: its tile (of TBM x BN) in the launch's linear order, the operand and result bases of its batch
+// entry, its k range as slabs of SLABK.
+template <int TBM, int SLABK>
+struct PairTile {
+    int tile_m, tile_n, m0, n0;
+    const char* A;
+    const char* B;
+    float* C;
+    int zsplit, zb;         // k-split (0 when batched) and batch entry (0 when not)
+    int kbeg, nslab;
+    __device__ __forceinline__ explicit PairTile(const PairArgs& g) {
+        int zidx;
+        pair_tile_map(g.M, g.N, g.tn, g.tm, g.tz, (int)blockIdx.x + g.tile0, tile_m, tile_n, zidx);
+        m0 = tile_m * TBM;
+        n0 = tile_n * BN;
+        A = g.A;
+        B = g.B;
+        C = g.C;
+        zsplit = zidx;
+        zb = 0;
+        if (g.batch > 1) {
+            A += (size_t)zidx * g.a_bs * 4;
+            B += (size_t)zidx * g.b_bs * 4;
+            C += (size_t)zidx * g.c_bs;
+            zsplit = 0;
+            zb = zidx;
+        }
+        kbeg = zsplit * g.k_per_split;
+        const int kend = min(g.K, kbeg + g.k_per_split);
+        nslab = (kend - kbeg) / SLABK;
+    }
+};
+
+// zero accumulators; the bias of this lane's output columns ncol0 + 32 j + (lane & 31) (consumed in the epilogue)
+__device__ __forceinline__ void pair_acc_init(const PairArgs& g, int ncol0, int lane, f32x16 (&acc)[MI][NI], float (&bvj)[NI]) {
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < NI; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+        const int n = ncol0 + j * 32 + (lane & 31);
+        bvj[j] = (g.bias != nullptr && n < g.N) ? g.bias[n] : 0.0f;
+    }
+}
+
+// The main loops are instantiated for MIV = 1 .. 4 valid 32-row sub-tiles of a wave's 128 rows: a wave of the ragged last M-tile whose
+// rows reach past M leaves out the sub-tiles that lie entirely outside (their fragment reads and MFMAs) - as a compile-time bound,
+// selected once per wave from the `rows` it has left.  Run-time `if (i < valid)` guards inside the one loop measured SLOWER (they break
+// the MFMA / LDS-read interleaving of every tile: Winograd forward at 857 rows 1.343 vs 1.221 ms, step 15.05 vs 14.66 ms); the four
+// instantiations: step 14.54 / 14.71 / 14.37 vs 14.63 / 14.76 / 14.50 ms (same box, interleaved), roofline.frac of the mix
+// 0.470 -> 0.480; alone the products gain 2-4 % at 1086 rows, the KC x MC one loses 3.6 % at 857 (tools/bench_gemm_pair.py).
+template <class Loop>
+__device__ __forceinline__ void for_valid_subtiles(int rows, Loop&& loop) {
+    switch (__builtin_amdgcn_readfirstlane(min(MI, (rows + 31) / 32))) {
+        case 1: loop(std::integral_constant<int, 1>{}); break;
+        case 2: loop(std::integral_constant<int, 2>{}); break;
+        case 3: loop(std::integral_constant<int, 3>{}); break;
+        default: loop(std::integral_constant<int, MI>{}); break;
+    }
+}
+
+// One wave's fragments of one 16-k step: h and l planes of MIV sub-tiles of A and NI of B (the l planes stay unused with ONEP)
+template <int MIV>
+struct PairFrags {
+    f16x8 ah[MIV > 0 ? MIV : 1], al[MIV > 0 ? MIV : 1], bh[NI], bl[NI];
+};
+
+// MIV x NI MFMAs: acc[i][j] += af[i] bf[j]
+template <int MIV>
+__device__ __forceinline__ void mma_cluster(f32x16 (&acc)[MI][NI], const f16x8 (&af)[MIV], const f16x8 (&bf)[NI]) {
+#pragma unroll
+    for (int i = 0; i < MIV; ++i)
+#pragma unroll
+        for (int j = 0; j < NI; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
+}
+
+// Pins the schedule of the code in front of it (since the last fence) to NMFMA MFMAs with NREAD LDS reads between them: one behind
+// each of the first MFMAs, what is left behind the last.
+template <int NMFMA, int NREAD>
+__device__ __forceinline__ void interleave_mfma_reads() {
+#pragma unroll
+    for (int q = 0; q < NMFMA; ++q) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        if (q < NREAD) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    }
+    if constexpr (NREAD > NMFMA) __builtin_amdgcn_sched_group_barrier(0x100, NREAD - NMFMA, 0);
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+template <int TBM, int SLABK>
+__device__ __forceinline__ void pair_epilogue(const PairArgs& g, const PairTile<TBM, SLABK>& T, f32x16 (&acc)[MI][NI], float (&bvj)[NI],
+                                              int wm, int wn, int lane) {
     // epilogue: undo the two scales (powers of two: exact), bias, ReLU.  Nothing may be in flight on the vector-memory counter
     // when the stores start: stores count on vmcnt as well, and a load whose completion the compiler cannot prove at a
     // control-flow join draws an s_waitcnt vmcnt(0) in front of EVERY guarded store (128 per lane, each then waiting for
@@ -317,10 +416,11 @@ __device__ __forceinline__ void pair_epilogue(const PairArgs& g, f32x16 (&acc)[M
     // tried: MFMA operands swapped so that the accumulator tile is the transpose and a lane stores four consecutive columns of
     // ITS row as 16 bytes - 32 stores per wave, no LDS: 1.33 vs 1.26 ms (32-byte pieces of 32 different rows per
     // instruction).  The stores themselves cost 4-8 % of a launch (ablation without them: 1.246 vs 1.303 ms).)
-    const float inv = 1.0f / (g.a_scale[zb] * g.b_scale[zb]);
+    const float inv = 1.0f / (g.a_scale[T.zb] * g.b_scale[T.zb]);
 #pragma unroll
     for (int j = 0; j < NI; ++j) asm volatile("" : "+v"(bvj[j]));
-    float* C = Cb + (size_t)zsplit * g.c_split_stride;
+    float* C = T.C + (size_t)T.zsplit * g.c_split_stride;
+    const int m0 = T.m0, n0 = T.n0;
     const int lk = lane >> 5, l31 = lane & 31;
     unsigned amax = 0;
     const bool relu = g.relu != 0;
@@ -334,7 +434,7 @@ __device__ __forceinline__ void pair_epilogue(const PairArgs& g, f32x16 (&acc)[M
                 for (int r = 0; r < 16; ++r) {
                     float v = acc[i][j][r] * inv + bvj[j];
                     if (relu) v = fmaxf(v, 0.0f);
-                    amax = max(amax, __float_as_uint(v) & 0x7fffffffu);
+                    amax = max(amax, abs_bits(v));
                     cj[(size_t)(i * 32 + (r & 3) + 8 * (r >> 2)) * g.ldc] = v;
                 }
             }
@@ -352,7 +452,7 @@ __device__ __forceinline__ void pair_epilogue(const PairArgs& g, f32x16 (&acc)[M
                     if (m >= g.M) continue;
                     float v = acc[i][j][r] * inv + bvj[j];
                     if (relu) v = fmaxf(v, 0.0f);
-                    amax = max(amax, __float_as_uint(v) & 0x7fffffffu);
+                    amax = max(amax, abs_bits(v));
                     C[(size_t)m * g.ldc + n] = v;
                 }
             }
@@ -375,32 +475,17 @@ __global__ __launch_bounds__(NT, NW / 4) void gemm_pair_kernel(const PairArgs g)
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int wm = wave / WNC, wn = wave % WNC;
-    int tile_m, tile_n, zidx;
-    pair_tile_map(g.M, g.N, g.tn, g.tm, g.tz, (int)blockIdx.x + g.tile0, tile_m, tile_n, zidx);
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
-    const char* Ab = g.A;
-    const char* Bb = g.B;
-    float* Cb = g.C;
-    int zsplit = zidx, zb = 0;
-    if (g.batch > 1) {
-        Ab += (size_t)zidx * g.a_bs * 4;
-        Bb += (size_t)zidx * g.b_bs * 4;
-        Cb += (size_t)zidx * g.c_bs;
-        zsplit = 0;
-        zb = zidx;
-    }
-    const int kbeg = zsplit * g.k_per_split;
-    const int kend = min(g.K, kbeg + g.k_per_split);
-    const int nslab = (kend - kbeg) / BK;
+    const PairTile<BM, BK> T(g);
+    const int nslab = T.nslab;
 
     using StageA = typename StageSel<AL, BM, IPW>::type;
     using StageB = typename StageSel<BL, BN, IPW>::type;
     StageA sa;
     StageB sb;
-    sa.init(m0, g.M, g.lda, wave, lane);
-    sb.init(n0, g.N, g.ldb, wave, lane);
-    const char* ak = Ab + (AL == L_KC ? (size_t)kbeg * 4 : (size_t)kbeg * g.lda * 4);
-    const char* bk = Bb + (BL == L_KC ? (size_t)kbeg * 4 : (size_t)kbeg * g.ldb * 4);
+    sa.init(T.m0, g.M, g.lda, wave, lane);
+    sb.init(T.n0, g.N, g.ldb, wave, lane);
+    const char* ak = T.A + (AL == L_KC ? (size_t)T.kbeg * 4 : (size_t)T.kbeg * g.lda * 4);
+    const char* bk = T.B + (BL == L_KC ? (size_t)T.kbeg * 4 : (size_t)T.kbeg * g.ldb * 4);
     const size_t a_adv = StageA::k_step_bytes(g.lda), b_adv = StageB::k_step_bytes(g.ldb);
 
     typename FragSel<AL, MI, BM>::type fa;
@@ -409,191 +494,94 @@ __global__ __launch_bounds__(NT, NW / 4) void gemm_pair_kernel(const PairArgs g)
     fb.init(wn * WN, lane);
 
     f32x16 acc[MI][NI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    float bvj[NI];
+    pair_acc_init(g, T.n0 + wn * WN, lane, acc, bvj);
 
-    float bvj[NI];          // bias of this lane's output columns (consumed in the epilogue)
+    // this wave's share of the next slab -> buffer `buf`
+    auto issue_slab = [&](const char* buf, auto with_a) __attribute__((always_inline)) {
+        if constexpr (decltype(with_a)::value) sa.issue(ak, buf, wave);
+        sb.issue(bk, buf + OPER, wave);
+        ak += a_adv;
+        bk += b_adv;
+    };
+    // prologue: slab 0 -> buffer 0 (waited for), slab 1 -> buffer 1 (in flight)
+    auto prologue = [&](auto with_a) __attribute__((always_inline)) {
+        issue_slab(smem, with_a);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (nslab > 1) issue_slab(smem + SLAB, with_a);
+    };
+    // The slab loop of a wave with MIV valid sub-tiles.  MIV = 0 is an idle wave (below): the same issue order and barrier sequence,
+    // no fragment reads, no MFMAs; of A it stages only what a working wave reads.
+    auto slab_loop = [&](auto miv_c) {
+        constexpr int MIV = decltype(miv_c)::value;
+        constexpr std::bool_constant<(MIV > 0 || AL == L_MC)> with_a{};
+        PairFrags<MIV> f0, f1;      // the fragments of a slab's first and second 16-k step
+        auto read = [&](PairFrags<MIV>& f, const char* buf, int ks, auto in_loop) __attribute__((always_inline)) {
+            if constexpr (MIV == 0) {
+            } else if constexpr (ABL_NO_LOOP_READS && decltype(in_loop)::value) {
+                asm volatile("" : "+v"(f.ah[0]), "+v"(f.al[0]), "+v"(f.bh[0]), "+v"(f.bl[0]));
+            } else {
 #pragma unroll
-    for (int j = 0; j < NI; ++j) {
-        const int n = n0 + wn * WN + j * 32 + (lane & 31);
-        bvj[j] = (g.bias != nullptr && n < g.N) ? g.bias[n] : 0.0f;
-    }
+                for (int j = 0; j < NI; ++j) {
+                    f.bh[j] = fb.read(buf + OPER, j, ks, 0);
+                    if constexpr (!ONEP) f.bl[j] = fb.read(buf + OPER, j, ks, 1);
+                }
+#pragma unroll
+                for (int i = 0; i < MIV; ++i) {
+                    if constexpr (!ONEP) f.al[i] = fa.read(buf, i, ks, 1);
+                    f.ah[i] = fa.read(buf, i, ks, 0);
+                }
+            }
+        };
+        // l * h + h * l + h * h of one 16-k step.  The scheduling fences around the MFMA clusters help the all-K-contiguous
+        // instantiation (+1 %) and cost the ones with a transposed-read operand 1.5-6 % (tools/bench_gemm_pair.py).  (Tried in round 6:
+        // the reads interleaved one to one with the MFMAs as in the ring kernel - with two waves per SIMD the other wave already fills
+        // those issue slots: +2.3 / 0 / +1.6 % and +0.4 / -0.2 / +0.9 % in two runs for a K-contiguous A, -1.7 % otherwise: noise.)
+        auto multiply = [&](const PairFrags<MIV>& f) __attribute__((always_inline)) {
+            if constexpr (MIV > 0) {
+                if constexpr (AL == L_KC && BL == L_KC) __builtin_amdgcn_sched_barrier(0);
+                if constexpr (!ONEP) {
+                    mma_cluster(acc, f.al, f.bh);
+                    mma_cluster(acc, f.ah, f.bl);
+                }
+                mma_cluster(acc, f.ah, f.bh);
+                if constexpr (AL == L_KC && BL == L_KC) __builtin_amdgcn_sched_barrier(0);
+            }
+        };
+        constexpr std::true_type in_loop{};
+        read(f0, smem, 0, std::false_type{});
+        if constexpr (ABL_NO_LOOP_READS) read(f1, smem, 1, std::false_type{});
+        for (int t = 0; t < nslab; ++t) {
+            const char* cur = smem + (t & 1) * SLAB;
+            const char* nxt = smem + ((t + 1) & 1) * SLAB;
+            // first 16-k step of slab t; its second step's fragments arrive meanwhile
+            read(f1, cur, 1, in_loop);
+            multiply(f0);
+            // every wave holds its fragments of slab t and its share of slab t+1 has landed: slab t+1 is complete and
+            // buffer t & 1 is free behind this barrier
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if constexpr (!ABL_NO_LOOP_DMA) {
+                if (t + 2 < nslab) issue_slab(cur, with_a);
+            }
+            if (t + 1 < nslab) read(f0, nxt, 0, in_loop);
+            multiply(f1);
+        }
+    };
     // Ragged last M-tile (800 ... 1200 proposals against 256-row tiles): when the tile's second 128 rows lie past M, the
     // four waves that own them (wm = 1) only stage their share of the operands and keep the barrier sequence - the
     // tile then costs its four working waves' MFMA time, about half a tile.  The working waves in turn leave out their 32-row
-    // sub-tiles past M (main_loop<MIV> below).
-#if CIM_PAIR_EXP != 6
-    if (wm == 1 && m0 + WM >= g.M) {
-        if constexpr (AL == L_MC) sa.issue(ak, smem, wave);
-        sb.issue(bk, smem + OPER, wave);
-        ak += a_adv;
-        bk += b_adv;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (nslab > 1) {
-            if constexpr (AL == L_MC) sa.issue(ak, smem + SLAB, wave);
-            sb.issue(bk, smem + SLAB + OPER, wave);
-            ak += a_adv;
-            bk += b_adv;
-        }
-        for (int t = 0; t < nslab; ++t) {
-            const char* cur = smem + (t & 1) * SLAB;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (t + 2 < nslab) {
-                if constexpr (AL == L_MC) sa.issue(ak, cur, wave);
-                sb.issue(bk, cur + OPER, wave);
-                ak += a_adv;
-                bk += b_adv;
-            }
-        }
+    // sub-tiles past M (for_valid_subtiles).
+    if (wm == 1 && T.m0 + WM >= g.M) {
+        prologue(std::bool_constant<AL == L_MC>{});
+        slab_loop(std::integral_constant<int, 0>{});
         return;
     }
-#endif
-    // prologue: slab 0 -> buffer 0 (waited for), slab 1 -> buffer 1 (in flight), first fragments of slab 0
-    sa.issue(ak, smem, wave);
-    sb.issue(bk, smem + OPER, wave);
-    ak += a_adv;
-    bk += b_adv;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (nslab > 1) {
-        sa.issue(ak, smem + SLAB, wave);
-        sb.issue(bk, smem + SLAB + OPER, wave);
-        ak += a_adv;
-        bk += b_adv;
-    }
+    prologue(std::true_type{});
+    for_valid_subtiles(g.M - T.m0 - wm * WM, slab_loop);
 
-    // The main loop, instantiated for MIV = 1 .. 4 valid 32-row sub-tiles of this wave's 128 rows: a working wave of the ragged last
-    // M-tile whose rows reach past M leaves out the sub-tiles that lie entirely outside (their fragment reads and MFMAs) - as a
-    // compile-time bound, selected once per workgroup.  Run-time `if (i < valid)` guards inside the one loop measured SLOWER (they
-    // break the MFMA / LDS-read interleaving of every tile: Winograd forward at 857 rows 1.343 vs 1.221 ms, step 15.05 vs 14.66 ms);
-    // the four instantiations: step 14.54 / 14.71 / 14.37 vs 14.63 / 14.76 / 14.50 ms (same box, interleaved), roofline.frac of the
-    // mix 0.470 -> 0.480; alone the products gain 2-4 % at 1086 rows, the KC x MC one loses 3.6 % at 857 (tools/bench_gemm_pair.py).
-    auto main_loop = [&](auto miv_c) {
-    constexpr int MIV = decltype(miv_c)::value;
-    f16x8 ah0[MIV], al0[MIV], bh0[NI], bl0[NI];
-    f16x8 ah1[MIV], al1[MIV], bh1[NI], bl1[NI];
-#define PAIR_READ(AH, AL_, BH, BL_, BUF, KS)                                                   \
-    _Pragma("unroll") for (int j = 0; j < NI; ++j) {                                           \
-        BH[j] = fb.read((BUF) + OPER, j, KS, 0);                                               \
-        if constexpr (!ONEP) BL_[j] = fb.read((BUF) + OPER, j, KS, 1);                         \
-    }                                                                                          \
-    _Pragma("unroll") for (int i = 0; i < MIV; ++i) {                                          \
-        if constexpr (!ONEP) AL_[i] = fa.read((BUF), i, KS, 1);                                \
-        AH[i] = fa.read((BUF), i, KS, 0);                                                      \
-    }
-#define PAIR_MMA(AF, BF)                                                                       \
-    _Pragma("unroll") for (int i = 0; i < MIV; ++i) _Pragma("unroll") for (int j = 0; j < NI; ++j) \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AF[i], BF[j], acc[i][j], 0, 0, 0)
-
-#if CIM_PAIR_EXP == 1
-#define PAIR_PRIO(x) __builtin_amdgcn_s_setprio(x)
-#else
-#define PAIR_PRIO(x)
-#endif
-// scheduling fences around the MFMA clusters: they help the all-K-contiguous instantiation (+1 %) and cost the ones with a
-// transposed-read operand 1.5-6 % (tools/bench_gemm_pair.py, CIM_PAIR_EXP=2 removes them everywhere)
-#if CIM_PAIR_EXP == 2
-#define PAIR_FENCE()
-#else
-#define PAIR_FENCE() if constexpr (AL == L_KC && BL == L_KC) __builtin_amdgcn_sched_barrier(0)
-#endif
-// Experiment switch (round 6): the half-step's fragment reads interleaved one to one with its MFMAs, as in the ring kernel, for the
-// instantiations with a K-contiguous A.  With two waves per SIMD the other wave already fills those issue slots: two interleaved runs of
-// tools/bench_gemm_pair.py gave +2.3 / 0 / +1.6 % and +0.4 / -0.2 / +0.9 % (Winograd forward / data gradient / fc1 forward), the
-// M-contiguous instantiations lose 1.7 % - within noise, not the product's build.
-#ifndef CIM_PAIR_SCHED
-#define CIM_PAIR_SCHED 0
-#endif
-#define PAIR_SCHED_ON (CIM_PAIR_SCHED && AL == L_KC)
-#if CIM_PAIR_SCHED
-#define PAIR_NREADS (((AL == L_KC ? 1 : 2) * MIV + (BL == L_KC ? 1 : 2) * NI) * (ONEP ? 1 : 2))
-#define PAIR_SCHED()                                                                           \
-    if constexpr (PAIR_SCHED_ON) {                                                             \
-        _Pragma("unroll") for (int q = 0; q < (ONEP ? 1 : 3) * MIV * NI; ++q) {                 \
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                 \
-            if (q < PAIR_NREADS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);            \
-        }                                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                     \
-    }
-#else
-#define PAIR_SCHED()
-#endif
-#if CIM_PAIR_EXP == 3 || CIM_PAIR_EXP == 5       /* ablation: no LDS-DMA in the loop */
-#define PAIR_ISSUE(A, B)
-#else
-#define PAIR_ISSUE(A, B) { sa.issue(ak, A, wave); sb.issue(bk, B, wave); ak += a_adv; bk += b_adv; }
-#endif
-#if CIM_PAIR_EXP == 4 || CIM_PAIR_EXP == 5       /* ablation: fragments stay in registers (MFMA only) */
-#define PAIR_READ_L(AH, AL_, BH, BL_, BUF, KS) asm volatile("" : "+v"(AH[0]), "+v"(AL_[0]), "+v"(BH[0]), "+v"(BL_[0]));
-#else
-#define PAIR_READ_L(AH, AL_, BH, BL_, BUF, KS) PAIR_READ(AH, AL_, BH, BL_, BUF, KS)
-#endif
-    PAIR_READ(ah0, al0, bh0, bl0, smem, 0)
-#if CIM_PAIR_EXP == 4 || CIM_PAIR_EXP == 5
-    PAIR_READ(ah1, al1, bh1, bl1, smem, 1)
-#endif
-    for (int t = 0; t < nslab; ++t) {
-        const char* cur = smem + (t & 1) * SLAB;
-        char* nxt = smem + ((t + 1) & 1) * SLAB;
-        // first 16-k step of slab t; its second step's fragments arrive meanwhile
-        PAIR_READ_L(ah1, al1, bh1, bl1, cur, 1)
-        PAIR_FENCE();
-        PAIR_PRIO(1);
-        if constexpr (!ONEP) {
-            PAIR_MMA(al0, bh0);
-            PAIR_MMA(ah0, bl0);
-        }
-        PAIR_MMA(ah0, bh0);
-        PAIR_SCHED();
-        PAIR_PRIO(0);
-        PAIR_FENCE();
-        // every wave holds its fragments of slab t and its share of slab t+1 has landed: slab t+1 is complete and
-        // buffer t & 1 is free behind this barrier
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (t + 2 < nslab) PAIR_ISSUE(cur, cur + OPER)
-        if (PAIR_SCHED_ON || t + 1 < nslab) {       /* (unconditional with the interleave - reads and MFMAs in ONE basic block; past the
-                                                        last slab it reads a buffer nobody writes any more) */
-            PAIR_READ_L(ah0, al0, bh0, bl0, nxt, 0)
-        }
-        PAIR_FENCE();
-        PAIR_PRIO(1);
-        if constexpr (!ONEP) {
-            PAIR_MMA(al1, bh1);
-            PAIR_MMA(ah1, bl1);
-        }
-        PAIR_MMA(ah1, bh1);
-        PAIR_SCHED();
-        PAIR_PRIO(0);
-        PAIR_FENCE();
-    }
-#undef PAIR_READ_L
-#undef PAIR_SCHED
-#undef PAIR_ISSUE
-#undef PAIR_FENCE
-#undef PAIR_PRIO
-#undef PAIR_READ
-#undef PAIR_MMA
-    };
-#if CIM_PAIR_EXP == 7
-    main_loop(std::integral_constant<int, MI>{});
-#else
-    switch (__builtin_amdgcn_readfirstlane(min(MI, (g.M - m0 - wm * WM + 31) / 32))) {
-        case 1: main_loop(std::integral_constant<int, 1>{}); break;
-        case 2: main_loop(std::integral_constant<int, 2>{}); break;
-        case 3: main_loop(std::integral_constant<int, 3>{}); break;
-        default: main_loop(std::integral_constant<int, MI>{}); break;
-    }
-#endif
-
-
-    pair_epilogue<BM>(g, acc, bvj, Cb, zsplit, zb, m0, n0, wm, wn, lane);
+    pair_epilogue(g, T, acc, bvj, wm, wn, lane);
 }
 
 // The co-resident form (`form` = 1): C tile 128 x 256, four waves (wave tile 128 x 64, one wave per SIMD), both operands K-major (the
@@ -602,104 +590,41 @@ __global__ __launch_bounds__(NT, NW / 4) void gemm_pair_kernel(const PairArgs g)
 // operands go through a RING of five 16-k slabs (24 KB each): the DMA of slab t + 4 is issued at step t and is waited for at step
 // t + 3 (s_waitcnt vmcnt(12): the two younger slabs stay in flight), one barrier per step of four waves.  Per output element the same
 // MFMA products in the same order as the kernel above: same bits.
+// (Tried: a fifth wave that issues every LDS-DMA instruction of the workgroup, the four others holding MFMAs and fragment reads only.
+// FASTER ALONE - 0.46-0.47 against 0.42-0.43 of the f16 peak, the 256 x 256 kernel's rate - and SLOWER WHERE IT IS USED: beside the
+// backbone's backward the last phase takes 3.69 ms with it, 3.60 without, the chains' kernels get less of the CU
+// (profiles/r6/gemm_pair_ring_kernel.txt).  Removed; DESIGN.md 4.1 names the last commit that has it.)
 template <bool ONEP>
 __global__ __launch_bounds__(RNT, 2) void gemm_pair_ring_kernel(const PairArgs g) {       // (2 waves per SIMD's worth of registers at most: <= 256)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int wn = wave;
-    int tile_m, tile_n, zidx;
-    pair_tile_map(g.M, g.N, g.tn, g.tm, g.tz, (int)blockIdx.x + g.tile0, tile_m, tile_n, zidx);
-    const int m0 = tile_m * RBM, n0 = tile_n * BN;
-    const char* Ab = g.A;
-    const char* Bb = g.B;
-    float* Cb = g.C;
-    int zsplit = zidx, zb = 0;
-    if (g.batch > 1) {
-        Ab += (size_t)zidx * g.a_bs * 4;
-        Bb += (size_t)zidx * g.b_bs * 4;
-        Cb += (size_t)zidx * g.c_bs;
-        zsplit = 0;
-        zb = zidx;
-    }
-    const int kbeg = zsplit * g.k_per_split;
-    const int kend = min(g.K, kbeg + g.k_per_split);
-    const int nslab = (kend - kbeg) / RBK;          // even (K and k_per_split are multiples of 32)
+    const PairTile<RBM, RBK> T(g);
+    const int nslab = T.nslab;          // even (K and k_per_split are multiples of 32)
 
-    const char* ak = Ab + (size_t)kbeg * g.lda * 4;
-    const char* bk = Bb + (size_t)kbeg * g.ldb * 4;
+    const char* ak = T.A + (size_t)T.kbeg * g.lda * 4;
+    const char* bk = T.B + (size_t)T.kbeg * g.ldb * 4;
     const size_t a_adv = (size_t)RBK * g.lda * 4, b_adv = (size_t)RBK * g.ldb * 4;
-#if CIM_RING_PRODUCER
-    // The producer wave: all 24 DMA instructions of a slab (8 of A, 16 of B), one slab per step behind the step's barrier; in front of
-    // the barrier of step t it waits for slab t + 1 (s_waitcnt vmcnt(48): slabs t + 2 and t + 3 stay in flight; the counter's 63 are
-    // exceeded right after an issue - the hardware holds the issue back, which only this wave waits for).
-    if (wave == 4) {
-        StageMC<RBM, 4 * RIPA, RBK> pa;
-        StageMC<BN, 4 * RIPB, RBK> pb;
-        pa.init(m0, g.M, g.lda, 0, lane);
-        pb.init(n0, g.N, g.ldb, 0, lane);
-        int left = nslab - 1;
-        for (int q = 0; q < RSTAGES - 1; ++q) {
-            pa.issue(ak, smem + q * RSTAGE, 0);
-            pb.issue(bk, smem + q * RSTAGE + RSTAGE_A, 0);
-            const bool more = left > 0;
-            ak += more ? a_adv : 0;
-            bk += more ? b_adv : 0;
-            left -= more ? 1 : 0;
-        }
-        asm volatile("s_waitcnt vmcnt(48)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        int wb = RSTAGES - 1;
-        for (int t = 0; t < nslab; ++t) {
-            asm volatile("s_waitcnt vmcnt(48)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            pa.issue(ak, smem + wb * RSTAGE, 0);
-            pb.issue(bk, smem + wb * RSTAGE + RSTAGE_A, 0);
-            const bool more = left > 0;
-            ak += more ? a_adv : 0;
-            bk += more ? b_adv : 0;
-            left -= more ? 1 : 0;
-            wb = wb == RSTAGES - 1 ? 0 : wb + 1;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        return;
-    }
-#else
     StageMC<RBM, RIPA, RBK> sa;
     StageMC<BN, RIPB, RBK> sb;
-    sa.init(m0, g.M, g.lda, wave, lane);
-    sb.init(n0, g.N, g.ldb, wave, lane);
-#endif
+    sa.init(T.m0, g.M, g.lda, wave, lane);
+    sb.init(T.n0, g.N, g.ldb, wave, lane);
     FragMC<MI, RBM> fa;
     FragMC<NI, BN> fb;
     fa.init(0, lane);
     fb.init(wn * WN, lane);
 
     f32x16 acc[MI][NI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
     float bvj[NI];
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-        const int n = n0 + wn * WN + j * 32 + (lane & 31);
-        bvj[j] = (g.bias != nullptr && n < g.N) ? g.bias[n] : 0.0f;
-    }
+    pair_acc_init(g, T.n0 + wn * WN, lane, acc, bvj);
 
     // Every step issues exactly one slab's DMA (six instructions per wave), so the wait in front of a step's barrier is always
     // vmcnt(12); past the last slab the source stays on the last one (re-read into buffers nobody consumes: 4 of K / 16 slabs) - no
     // branch around the issue, the step is one basic block.  `left` = slabs the source pointers can still advance by.
-#if !CIM_RING_PRODUCER
     int left = nslab - 1;
-    auto advance = [&]() {
-#if CIM_RING_DBG == 7     /* ablation: the DMA re-reads slab 0 for ever (its mechanics with constant data) */
-        const bool more = false;
-#else
+    auto advance = [&]() __attribute__((always_inline)) {
         const bool more = left > 0;
-#endif
         ak += more ? a_adv : 0;
         bk += more ? b_adv : 0;
         left -= more ? 1 : 0;
@@ -713,148 +638,86 @@ __global__ __launch_bounds__(RNT, 2) void gemm_pair_ring_kernel(const PairArgs g
     }
     asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
     __syncthreads();
-#define RING_WAIT() asm volatile("s_waitcnt vmcnt(12)" ::: "memory")
-#define RING_ISSUE_A() sa.issue(ak, wbuf, wave)
-#define RING_ISSUE_B(H) sb.issue_pair(bk, wbuf + RSTAGE_A, wave, H)
-#define RING_ADVANCE() advance()
-#else
-    __builtin_amdgcn_s_barrier();       // (slab 0 has landed: the producer waited for it)
-#define RING_WAIT()
-#define RING_ISSUE_A()
-#define RING_ISSUE_B(H)
-#define RING_ADVANCE()
-#endif
 
     auto main_loop = [&](auto miv_c) {
-    constexpr int MIV = decltype(miv_c)::value;
-    f16x8 ah0[MIV], al0[MIV], bh0[NI], bl0[NI];
-    f16x8 ah1[MIV], al1[MIV], bh1[NI], bl1[NI];
-#define RING_READ_B(BH, BL_, BUF)                                                              \
-    _Pragma("unroll") for (int j = 0; j < NI; ++j) {                                           \
-        BH[j] = fb.read((BUF) + RSTAGE_A, j, 0, 0);                                            \
-        if constexpr (!ONEP) BL_[j] = fb.read((BUF) + RSTAGE_A, j, 0, 1);                      \
-    }
-#define RING_READ_A(AF, BUF, PL)                                                               \
-    _Pragma("unroll") for (int i = 0; i < MIV; ++i) AF[i] = fa.read((BUF), i, 0, PL);
-#if CIM_RING_DBG == 5 || CIM_RING_DBG == 6      /* ablation: the loop's fragment reads are left out (registers keep the first slab's) */
-#define RING_LREAD_B(BH, BL_, BUF) asm volatile("" : "+v"(BH[0]), "+v"(BL_[0]));
-#define RING_LREAD_A(AF, BUF, PL) asm volatile("" : "+v"(AF[0]));
-#else
-#define RING_LREAD_B(BH, BL_, BUF) RING_READ_B(BH, BL_, BUF)
-#define RING_LREAD_A(AF, BUF, PL) RING_READ_A(AF, BUF, PL)
-#endif
-#define RING_MMA(AF, BF)                                                                       \
-    _Pragma("unroll") for (int i = 0; i < MIV; ++i) _Pragma("unroll") for (int j = 0; j < NI; ++j) \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AF[i], BF[j], acc[i][j], 0, 0, 0)
-// With ONE wave per SIMD nothing else fills the matrix pipe while this wave issues LDS reads or DMA: a step is three groups of
-// MIV * NI MFMAs, each interleaved one to one with a third of the NEXT step's fragment reads (no dependence), and the step's six DMA
-// instructions go out in three pieces BETWEEN the groups (a piece issues while the group's last MFMA executes).  Fused ahead of the
-// MFMAs as a block (reads, then DMA) the same kernel ran at 0.36 of the f16 peak, interleaved 0.39+ (fc1's weight gradient).
-#if CIM_RING_SCHED == 0
-#define RING_SCHED(NREAD)
-#else
-#define RING_SCHED(NREAD)                                                                      \
-    _Pragma("unroll") for (int q = 0; q < MIV * NI; ++q) {                                     \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                     \
-        if (q < (NREAD)) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                    \
-    }                                                                                          \
-    if ((NREAD) > MIV * NI) __builtin_amdgcn_sched_group_barrier(0x100, (NREAD) - MIV * NI, 0);\
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-// The step's barrier orders (i) every wave's part of slab T + 1 having landed (each wave waits for its own DMA in front of it) and (ii)
-// the DMA of this step against the fragment reads of the buffer it overwrites - those were issued two steps ago and consumed by the last
-// step's MFMAs.  The fragment reads still in flight (slab T's last ones) touch a buffer nobody writes before the NEXT barrier, by when this
-// step's MFMAs have consumed them: the bare s_barrier is enough, __syncthreads()'s s_waitcnt lgkmcnt(0) in front of it would expose
-// those reads' latency on every step (one wave per SIMD: nothing else runs meanwhile).
-#if CIM_RING_SCHED == 2
-#define RING_BARRIER() __syncthreads()
-#else
-#define RING_BARRIER() __builtin_amdgcn_s_barrier()
-#endif
-// one 16-k step: slab T + 1 has landed behind the barrier and buffer (T - 1) % 5 is free (its fragments went into registers at
-// step T - 2): issue slab T + 4 into it, fetch the fragments of slab T + 1, multiply those of slab T
-#define RING_STEP(AH, AL_, BH, BL_, NAH, NAL, NBH, NBL)                                        \
-    {                                                                                          \
-        RING_WAIT();                                                                           \
-        RING_BARRIER();                                                                        \
-        const char* nxt = smem + rb * RSTAGE;                                                  \
-        const char* wbuf = smem + wb * RSTAGE;                                                 \
-        if constexpr (ONEP) {                                                                  \
-            RING_ISSUE_A();                                                                    \
-            RING_ISSUE_B(0);                                                                   \
-            RING_ISSUE_B(1);                                                                   \
-            RING_LREAD_B(NBH, NBL, nxt)                                                         \
-            RING_LREAD_A(NAH, nxt, 0)                                                           \
-            RING_MMA(AH, BH);                                                                  \
-            RING_SCHED(2 * NI + 2 * MIV)                                                       \
-        } else {                                                                               \
-            RING_LREAD_B(NBH, NBL, nxt)                                                         \
-            RING_MMA(AL_, BH);                                                                 \
-            RING_SCHED(4 * NI)                                                                 \
-            RING_ISSUE_A();                                                                    \
-            __builtin_amdgcn_sched_barrier(0);                                                 \
-            RING_LREAD_A(NAL, nxt, 1)                                                           \
-            RING_MMA(AH, BL_);                                                                 \
-            RING_SCHED(2 * MIV)                                                                \
-            RING_ISSUE_B(0);                                                                   \
-            __builtin_amdgcn_sched_barrier(0);                                                 \
-            RING_LREAD_A(NAH, nxt, 0)                                                           \
-            RING_MMA(AH, BH);                                                                  \
-            RING_SCHED(2 * MIV)                                                                \
-            RING_ISSUE_B(1);                                                                   \
-        }                                                                                      \
-        RING_ADVANCE();                                                                        \
-        (void)wbuf;                                                                            \
-        wb = wb == RSTAGES - 1 ? 0 : wb + 1;                                                   \
-        rb = rb == RSTAGES - 1 ? 0 : rb + 1;                                                   \
-    }
-    RING_READ_B(bh0, bl0, smem)
-    if constexpr (!ONEP) { RING_READ_A(al0, smem, 1) }
-    RING_READ_A(ah0, smem, 0)
-#if CIM_RING_DBG == 5 || CIM_RING_DBG == 6
-    RING_READ_B(bh1, bl1, smem)
-    if constexpr (!ONEP) { RING_READ_A(al1, smem, 1) }
-    RING_READ_A(ah1, smem, 0)
-#endif
-    int rb = 1, wb = RSTAGES - 1;           // buffers of slab t + 1 (read) and slab t + 4 (written)
-    for (int t = 0; t < nslab; t += 2) {
-        RING_STEP(ah0, al0, bh0, bl0, ah1, al1, bh1, bl1)
-        RING_STEP(ah1, al1, bh1, bl1, ah0, al0, bh0, bl0)
-    }
-#undef RING_STEP
-#undef RING_WAIT
-#undef RING_ISSUE_A
-#undef RING_ISSUE_B
-#undef RING_ADVANCE
-#undef RING_BARRIER
-#undef RING_SCHED
-#undef RING_MMA
-#undef RING_READ_A
-#undef RING_LREAD_A
-#undef RING_LREAD_B
-#undef RING_READ_B
+        constexpr int MIV = decltype(miv_c)::value;
+        PairFrags<MIV> f0, f1;          // the fragments of even and odd slabs
+        auto read_b = [&](PairFrags<MIV>& f, const char* buf) __attribute__((always_inline)) {
+#pragma unroll
+            for (int j = 0; j < NI; ++j) {
+                f.bh[j] = fb.read(buf + RSTAGE_A, j, 0, 0);
+                if constexpr (!ONEP) f.bl[j] = fb.read(buf + RSTAGE_A, j, 0, 1);
+            }
+        };
+        auto read_a = [&](f16x8 (&af)[MIV], const char* buf, int pl) __attribute__((always_inline)) {
+#pragma unroll
+            for (int i = 0; i < MIV; ++i) af[i] = fa.read(buf, i, 0, pl);
+        };
+        int rb = 1, wb = RSTAGES - 1;           // buffers of slab t + 1 (read) and slab t + 4 (written)
+        // One 16-k step: slab t + 1 has landed behind the barrier and buffer (t - 1) % 5 is free (its fragments went into registers at
+        // step t - 2): issue slab t + 4 into it, fetch the fragments `nf` of slab t + 1, multiply those of slab t (`f`).
+        // With ONE wave per SIMD nothing else fills the matrix pipe while this wave issues LDS reads or DMA: a step is three groups of
+        // MIV * NI MFMAs, each interleaved one to one with a third of the NEXT step's fragment reads (no dependence), and the step's six
+        // DMA instructions go out in three pieces BETWEEN the groups (a piece issues while the group's last MFMA executes).  Fused ahead
+        // of the MFMAs as a block (reads, then DMA) the same kernel ran at 0.36 of the f16 peak, interleaved 0.39+ (fc1's weight gradient).
+        // The step's barrier orders (i) every wave's part of slab t + 1 having landed (each wave waits for its own DMA in front of it)
+        // and (ii) the DMA of this step against the fragment reads of the buffer it overwrites - those were issued two steps ago and
+        // consumed by the last step's MFMAs.  The fragment reads still in flight (slab t's last ones) touch a buffer nobody writes before
+        // the NEXT barrier, by when this step's MFMAs have consumed them: the bare s_barrier is enough, __syncthreads()'s s_waitcnt
+        // lgkmcnt(0) in front of it would expose those reads' latency on every step (one wave per SIMD: nothing else runs meanwhile).
+        auto step = [&](const PairFrags<MIV>& f, PairFrags<MIV>& nf) __attribute__((always_inline)) {
+            asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            const char* nxt = smem + rb * RSTAGE;
+            const char* wbuf = smem + wb * RSTAGE;
+            if constexpr (ONEP) {
+                sa.issue(ak, wbuf, wave);
+                sb.issue_pair(bk, wbuf + RSTAGE_A, wave, 0);
+                sb.issue_pair(bk, wbuf + RSTAGE_A, wave, 1);
+                read_b(nf, nxt);
+                read_a(nf.ah, nxt, 0);
+                mma_cluster(acc, f.ah, f.bh);
+                interleave_mfma_reads<MIV * NI, 2 * NI + 2 * MIV>();
+            } else {
+                read_b(nf, nxt);
+                mma_cluster(acc, f.al, f.bh);
+                interleave_mfma_reads<MIV * NI, 4 * NI>();
+                sa.issue(ak, wbuf, wave);
+                __builtin_amdgcn_sched_barrier(0);
+                read_a(nf.al, nxt, 1);
+                mma_cluster(acc, f.ah, f.bl);
+                interleave_mfma_reads<MIV * NI, 2 * MIV>();
+                sb.issue_pair(bk, wbuf + RSTAGE_A, wave, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                read_a(nf.ah, nxt, 0);
+                mma_cluster(acc, f.ah, f.bh);
+                interleave_mfma_reads<MIV * NI, 2 * MIV>();
+                sb.issue_pair(bk, wbuf + RSTAGE_A, wave, 1);
+            }
+            advance();
+            wb = wb == RSTAGES - 1 ? 0 : wb + 1;
+            rb = rb == RSTAGES - 1 ? 0 : rb + 1;
+        };
+        read_b(f0, smem);
+        if constexpr (!ONEP) read_a(f0.al, smem, 1);
+        read_a(f0.ah, smem, 0);
+        for (int t = 0; t < nslab; t += 2) {
+            step(f0, f1);
+            step(f1, f0);
+        }
     };
-    switch (__builtin_amdgcn_readfirstlane(min(MI, (g.M - m0 + 31) / 32))) {
-        case 1: main_loop(std::integral_constant<int, 1>{}); break;
-        case 2: main_loop(std::integral_constant<int, 2>{}); break;
-        case 3: main_loop(std::integral_constant<int, 3>{}); break;
-        default: main_loop(std::integral_constant<int, MI>{}); break;
-    }
+    for_valid_subtiles(g.M - T.m0, main_loop);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the re-read slabs of the last steps: nothing may be in flight when the stores start)
-#if CIM_RING_DBG != 1
-    pair_epilogue<RBM>(g, acc, bvj, Cb, zsplit, zb, m0, n0, 0, wn, lane);
-#endif
+    pair_epilogue(g, T, acc, bvj, 0, wn, lane);
 }
 
-// split-K reduce: fixed order, bias, ReLU, optional max |C|.  Round 6: a launch of at most 1024 workgroups that WALK over the result,
-// and ONE max |C| atomic per workgroup (through LDS) instead of one per wave of a launch with a workgroup per 1024 elements - the
-// fc1 forward's reduce (4 M elements: 16 k waves) took 54-77 us in the step for 80 MB: its first ~2000 resident waves all see a
-// zero word and fire their atomicMax on ONE address (~12 ns each in L2); the same kernel without max |C| takes 13 us.
+// split-K reduce: fixed order, bias, ReLU, optional max |C|.  Round 6: a launch of at most 1024 workgroups that WALK over the result
+// (and one max |C| atomic per workgroup: block_amax_publish) instead of a launch with a workgroup per 1024 elements - the fc1 forward's
+// reduce is 4 M elements = 16 k waves, 80 MB.
 __global__ __launch_bounds__(256) void pair_splitk_reduce_kernel(const float* __restrict__ ws, float* __restrict__ C,
                                                                  const float* __restrict__ bias, int M, int N, int ldc,
                                                                  int splits, long long stride, int relu,
                                                                  unsigned* __restrict__ c_amax) {
-    __shared__ unsigned s_am[4];
     const long long total = (long long)M * N;
     unsigned am = 0;
     for (long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; i < total; i += (long long)gridDim.x * 1024) {
@@ -877,15 +740,9 @@ __global__ __launch_bounds__(256) void pair_splitk_reduce_kernel(const float* __
             s.x = fmaxf(s.x, 0.f); s.y = fmaxf(s.y, 0.f); s.z = fmaxf(s.z, 0.f); s.w = fmaxf(s.w, 0.f);
         }
         *reinterpret_cast<float4*>(C + (size_t)m * ldc + n) = s;
-        am = max(am, max(max(__float_as_uint(s.x) & 0x7fffffffu, __float_as_uint(s.y) & 0x7fffffffu),
-                         max(__float_as_uint(s.z) & 0x7fffffffu, __float_as_uint(s.w) & 0x7fffffffu)));
+        am = max(am, abs_bits_max4(s));
     }
-    if (c_amax != nullptr) {
-        am = wave_max_u32(am);
-        if ((threadIdx.x & 63) == 0) s_am[threadIdx.x >> 6] = am;
-        __syncthreads();
-        if (threadIdx.x == 0) cim::amax_publish(c_amax, max(max(s_am[0], s_am[1]), max(s_am[2], s_am[3])));
-    }
+    if (c_amax != nullptr) block_amax_publish(c_amax, am);
 }
 
 // ---- producers of pair images ---------------------------------------------------------------------------
@@ -913,19 +770,12 @@ __global__ __launch_bounds__(256) void pair_masked_stats_kernel(const float* __r
                 const float4 v = *reinterpret_cast<const float4*>(y + (size_t)r * cols + col);
                 const float4 z = make_float4(v.x > 0.f ? g.x : 0.f, v.y > 0.f ? g.y : 0.f, v.z > 0.f ? g.z : 0.f, v.w > 0.f ? g.w : 0.f);
                 s.x += z.x; s.y += z.y; s.z += z.z; s.w += z.w;
-                m = max(m, max(max(__float_as_uint(z.x) & 0x7fffffffu, __float_as_uint(z.y) & 0x7fffffffu),
-                               max(__float_as_uint(z.z) & 0x7fffffffu, __float_as_uint(z.w) & 0x7fffffffu)));
+                m = max(m, abs_bits_max4(z));
             }
         }
     }
-    // ONE atomicMax per workgroup (round 6; was one per wave: the ~2000 waves that are resident when the launch starts all see a
-    // zero word and fire on one address at ~12 ns each - 65 / 35 us for the two 32 MB launches of the step)
-    __shared__ unsigned s_m[4];
-    m = wave_max_u32(m);
-    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
     if (part != nullptr) red[ry][cx] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) cim::amax_publish(amax, max(max(s_m[0], s_m[1]), max(s_m[2], s_m[3])));
+    block_amax_publish(amax, m);        // (its barrier is the one the partial sums in red[][] need as well)
     if (part == nullptr) return;
     if (ry == 0 && col < cols) {
         float4 t = red[0][cx];
@@ -983,16 +833,12 @@ __global__ __launch_bounds__(256) void pair_split_kernel(const float* __restrict
 // max |x| of a dense fp32 array as a bit pattern (atomicMax into a caller-zeroed word)
 __global__ __launch_bounds__(256) void pair_amax_kernel(const float* __restrict__ X, long long n4, int tail, unsigned* __restrict__ out) {
     unsigned m = 0;
-    if (blockIdx.x == 0 && (int)threadIdx.x < tail) m = __float_as_uint(X[n4 * 4 + threadIdx.x]) & 0x7fffffffu;
+    if (blockIdx.x == 0 && (int)threadIdx.x < tail) m = abs_bits(X[n4 * 4 + threadIdx.x]);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
         const uint4 v = *reinterpret_cast<const uint4*>(X + i * 4);
-        m = max(m, max(max(v.x & 0x7fffffffu, v.y & 0x7fffffffu), max(v.z & 0x7fffffffu, v.w & 0x7fffffffu)));
+        m = max(m, abs_bits_max4(v));
     }
-    __shared__ unsigned s_m[4];
-    m = wave_max_u32(m);
-    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) cim::amax_publish(out, max(max(s_m[0], s_m[1]), max(s_m[2], s_m[3])));      // one atomic per workgroup
+    block_amax_publish(out, m);
 }
 
 template <int AL, int BL, bool RING>
@@ -1056,6 +902,26 @@ int dispatch_pair(const PairArgs& g, int a_mcontig, int b_kcontig, int splits, f
 
 }  // namespace
 
+// the fields both entry points set; everything else (bias, ReLU, batch, c_amax; the launch's k_per_split, split stride and tile grid) is
+// zero / null / one batch entry until the entry point or launch_pair says otherwise
+static PairArgs pair_args(const void* A, const void* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* a_scale,
+                          const float* b_scale) {
+    PairArgs g{};
+    g.A = (const char*)A;
+    g.B = (const char*)B;
+    g.C = C;
+    g.M = M;
+    g.N = N;
+    g.K = K;
+    g.lda = lda;
+    g.ldb = ldb;
+    g.ldc = ldc;
+    g.batch = 1;
+    g.a_scale = a_scale;
+    g.b_scale = b_scale;
+    return g;
+}
+
 static bool pair_dims_ok(int M, int N, int K, int lda, int ldb, int ldc, int a_mcontig, int b_kcontig) {
     if (M <= 0 || N <= 0 || K <= 0 || K % 32 != 0 || N % 4 != 0 || ldc % 4 != 0 || ldc < N) return false;
     if (lda % 8 != 0 || ldb % 8 != 0) return false;
@@ -1095,7 +961,10 @@ extern "C" int cim_gemm_pair(const void* A, const void* B, float* C, const float
     CIM_CHECK_ARG(form == 0 || (form == 1 && a_mcontig && !b_kcontig));
     CIM_CHECK_ARG(pair_dims_ok(M, N, K, lda, ldb, ldc, a_mcontig, b_kcontig));
     CIM_CHECK_ARG(splits <= 1 || workspace != nullptr);
-    PairArgs g{(const char*)A, (const char*)B, C, bias, M, N, K, lda, ldb, ldc, relu, 0, 0, 1, 0, 0, 0, a_scale, b_scale, c_amax, 0, 0, 0, 0};
+    PairArgs g = pair_args(A, B, C, M, N, K, lda, ldb, ldc, a_scale, b_scale);
+    g.bias = bias;
+    g.relu = relu;
+    g.c_amax = c_amax;
     int rc = dispatch_pair(g, a_mcontig, b_kcontig, splits, workspace, cim::as_stream(stream), max_workgroups, products, form);
     if (rc) { cim::set_error("cim_gemm_pair: launch setup failed (%d)", rc); return rc; }
     CIM_CHECK_LAUNCH();
@@ -1110,7 +979,11 @@ extern "C" int cim_gemm_pair_batched(const void* A, const void* B, float* C, int
     CIM_CHECK_ARG(form == 0 || (form == 1 && a_mcontig && !b_kcontig));
     CIM_CHECK_ARG(pair_dims_ok(M, N, K, lda, ldb, ldc, a_mcontig, b_kcontig));
     CIM_CHECK_ARG(a_bs % 8 == 0 && b_bs % 8 == 0 && c_bs % 4 == 0);
-    PairArgs g{(const char*)A, (const char*)B, C, nullptr, M, N, K, lda, ldb, ldc, 0, 0, 0, batch, a_bs, b_bs, c_bs, a_scale, b_scale, nullptr, 0, 0, 0, 0};
+    PairArgs g = pair_args(A, B, C, M, N, K, lda, ldb, ldc, a_scale, b_scale);
+    g.batch = batch;
+    g.a_bs = a_bs;
+    g.b_bs = b_bs;
+    g.c_bs = c_bs;
     int rc = dispatch_pair(g, a_mcontig, b_kcontig, 1, nullptr, cim::as_stream(stream), max_workgroups, products, form);
     if (rc) { cim::set_error("cim_gemm_pair_batched: launch setup failed (%d)", rc); return rc; }
     CIM_CHECK_LAUNCH();

@@ -27,8 +27,9 @@ args = ap.parse_args()
 
 dev = torch.device("cuda:0")
 lib = _lib.load()
-# ablation / variant builds of the library next to the product one (python -m cim_amd.build --out=cim_amd/libcim_hip_alt<tag>.so
-# with CIM_HIPCC_FLAGS=-DCIM_PAIR_EXP=n): their pair GEMMs are timed in the same interleaved rounds
+# ablation / variant builds of the library next to the product one (tools/build_alt.sh exp3|exp4|exp5 gemm_pair.hip -DCIM_PAIR_EXP=3|4|5:
+# no LDS-DMA in the slab loop / MFMA only / both; or any cim_amd/libcim_hip_alt<tag>.so): their pair GEMMs are timed in the same
+# interleaved rounds
 import ctypes
 import glob
 alts = {}
@@ -95,32 +96,56 @@ def _amax(x, rows, cols, ld, want_rows, want_cols, batch=1, bs=0):
 
 cases = {}
 PRODUCTS = 1 if args.one_product else 3      # --one-product: the h * h term alone (TF32-class, extra.tf32_class of bench.py)
-sp = lambda m, n, k: lib.cim_gemm_pair_splits(m, n, k)
 fl_conv = NPOS * 2.0 * N * 2 * C * C
 fl_fc = 2.0 * N * K1 * 4096
-cases["pair wino_fwd   (KC x MC)"] = (lambda: lib.cim_gemm_pair_batched(P(pV.buf), P(pU.buf), P(M), N, C, 2 * C, 2 * C, C, C, 0, 0, NPOS, pV.bs, pU.bs, N * C, P(pV.scale), P(pU.scale), 0, PRODUCTS, 0, st), fl_conv)
-cases["pair wino_dgrad (KC x KC)"] = (lambda: lib.cim_gemm_pair_batched(P(pD.buf), P(pU.buf), P(M2), N, 2 * C, C, C, C, 2 * C, 0, 1, NPOS, pD.bs, pU.bs, N * 2 * C, P(pD.scale), P(pU.scale), 0, PRODUCTS, 0, st), fl_conv)
-cases["pair wino_wgrad (MC x MC)"] = (lambda: lib.cim_gemm_pair_batched(P(pV.buf), P(pD.buf), P(dU), 2 * C, C, NP, 2 * C, C, C, 1, 0, NPOS, pV.bs, pD.bs, 2 * C * C, P(pV.scale), P(pD.scale), 0, PRODUCTS, 0, st), fl_conv)
-cases["pair fc1_fwd    (KC x KC)"] = (lambda: lib.cim_gemm_pair(P(pX.buf), P(pW.buf), P(y1), None, N, 4096, K1, K1, K1, 4096, 0, 1, 0, sp(N, 4096, K1), P(ws), P(pX.scale), P(pW.scale), None, 0, PRODUCTS, 0, st), fl_fc)
-cases["pair fc1_dgrad  (KC x MC)"] = (lambda: lib.cim_gemm_pair(P(pY.buf), P(pW.buf), P(dx1), None, N, K1, 4096, 4096, K1, K1, 0, 0, 0, 1, None, P(pY.scale), P(pW.scale), None, 0, PRODUCTS, 0, st), fl_fc)
-cases["pair fc1_wgrad  (MC x MC)"] = (lambda: lib.cim_gemm_pair(P(pY.buf), P(pX.buf), P(dw1), None, 4096, K1, NP, 4096, K1, K1, 1, 0, 0, 1, None, P(pY.scale), P(pX.scale), None, 0, PRODUCTS, 0, st), fl_fc)
-# the co-resident form (128 x 256 tiles of four waves) of the two weight-gradient products
-cases["form1 wino_wgrad"] = (lambda: lib.cim_gemm_pair_batched(P(pV.buf), P(pD.buf), P(dU), 2 * C, C, NP, 2 * C, C, C, 1, 0, NPOS, pV.bs, pD.bs, 2 * C * C, P(pV.scale), P(pD.scale), 0, PRODUCTS, 1, st), fl_conv)
-cases["form1 fc1_wgrad"] = (lambda: lib.cim_gemm_pair(P(pY.buf), P(pX.buf), P(dw1), None, 4096, K1, NP, 4096, K1, K1, 1, 0, 0, 1, None, P(pY.scale), P(pX.scale), None, 0, PRODUCTS, 1, st), fl_fc)
+
+
+def product_cases(L):
+    """The step's eight pair products as calls into library L: short name -> (call, flops).  `fc1_wgrad` (form, launches of at
+    most `lim` workgroups) is also returned for the diagnosis rows."""
+    sp = L.cim_gemm_pair_splits
+
+    def wino(a, b, out, m, n, k, a_m, b_k, form=0):
+        return lambda: L.cim_gemm_pair_batched(P(a.buf), P(b.buf), P(out), m, n, k, a.ld, b.ld, n, a_m, b_k, NPOS, a.bs, b.bs, m * n,
+                                               P(a.scale), P(b.scale), 0, PRODUCTS, form, st)
+
+    def fc(a, b, out, m, n, k, a_m, b_k, form=0, splits=1, lim=0):
+        return lambda: L.cim_gemm_pair(P(a.buf), P(b.buf), P(out), None, m, n, k, a.ld, b.ld, n, a_m, b_k, 0, splits,
+                                       P(ws) if splits > 1 else None, P(a.scale), P(b.scale), None, lim, PRODUCTS, form, st)
+
+    def fc1_wgrad(form, lim=0):
+        return fc(pY, pX, dw1, 4096, K1, NP, 1, 0, form, lim=lim)
+
+    return {
+        "wino_fwd": (wino(pV, pU, M, N, C, 2 * C, 0, 0), fl_conv),
+        "wino_dgrad": (wino(pD, pU, M2, N, 2 * C, C, 0, 1), fl_conv),
+        "wino_wgrad": (wino(pV, pD, dU, 2 * C, C, NP, 1, 0), fl_conv),
+        "fc1_fwd": (fc(pX, pW, y1, N, 4096, K1, 0, 1, splits=sp(N, 4096, K1)), fl_fc),
+        "fc1_dgrad": (fc(pY, pW, dx1, N, K1, 4096, 0, 0), fl_fc),
+        "fc1_wgrad": (fc1_wgrad(0), fl_fc),
+        # the co-resident form (128 x 256 tiles of four waves) of the two weight-gradient products
+        "form1 wino_wgrad": (wino(pV, pD, dU, 2 * C, C, NP, 1, 0, form=1), fl_conv),
+        "form1 fc1_wgrad": (fc1_wgrad(1), fl_fc),
+    }, fc1_wgrad
+
+
+# row names: refresh_profiles.sh and pmc_summary.py select cases by them
+PRODUCT_ROWS = {"wino_fwd": "pair wino_fwd   (KC x MC)", "wino_dgrad": "pair wino_dgrad (KC x KC)", "wino_wgrad": "pair wino_wgrad (MC x MC)",
+                "fc1_fwd": "pair fc1_fwd    (KC x KC)", "fc1_dgrad": "pair fc1_dgrad  (KC x MC)", "fc1_wgrad": "pair fc1_wgrad  (MC x MC)",
+                "form1 wino_wgrad": "form1 wino_wgrad", "form1 fc1_wgrad": "form1 fc1_wgrad"}
+ALT_ROWS = ("wino_fwd", "wino_dgrad", "wino_wgrad", "fc1_fwd", "form1 wino_wgrad", "form1 fc1_wgrad", "fc1_dgrad", "fc1_wgrad")
+pc, fc1_wgrad = product_cases(lib)
+for short, name in PRODUCT_ROWS.items():
+    cases[name] = pc[short]
 if os.environ.get("CIM_BENCH_FORM1_LIMITS"):        # (diagnosis: per-CU latency or shared bandwidth?  launches of n workgroups)
     for lim in (64, 128, 256, 512):
-        cases["form1 fc1_wgrad launches of %d" % lim] = (lambda lim=lim: lib.cim_gemm_pair(P(pY.buf), P(pX.buf), P(dw1), None, 4096, K1, NP, 4096, K1, K1, 1, 0, 0, 1, None, P(pY.scale), P(pX.scale), None, lim, PRODUCTS, 1, st), fl_fc)
-        cases["pair fc1_wgrad launches of %d" % lim] = (lambda lim=lim: lib.cim_gemm_pair(P(pY.buf), P(pX.buf), P(dw1), None, 4096, K1, NP, 4096, K1, K1, 1, 0, 0, 1, None, P(pY.scale), P(pX.scale), None, lim, PRODUCTS, 0, st), fl_fc)
+        cases["form1 fc1_wgrad launches of %d" % lim] = (fc1_wgrad(1, lim), fl_fc)
+        cases["pair fc1_wgrad launches of %d" % lim] = (fc1_wgrad(0, lim), fl_fc)
 cases["split V (generic producer)"] = (lambda: lib.cim_pair_split(P(V), P(pV.buf), NP, NP, 2 * C, 2 * C, 2 * C, NPOS, NP * 2 * C, pV.bs, P(pV.scale), None, st), 0.0)
 for tag, al in alts.items():
-    cases["%-4s wino_fwd" % tag] = (lambda al=al: al.cim_gemm_pair_batched(P(pV.buf), P(pU.buf), P(M), N, C, 2 * C, 2 * C, C, C, 0, 0, NPOS, pV.bs, pU.bs, N * C, P(pV.scale), P(pU.scale), 0, PRODUCTS, 0, st), fl_conv)
-    cases["%-4s wino_dgrad" % tag] = (lambda al=al: al.cim_gemm_pair_batched(P(pD.buf), P(pU.buf), P(M2), N, 2 * C, C, C, C, 2 * C, 0, 1, NPOS, pD.bs, pU.bs, N * 2 * C, P(pD.scale), P(pU.scale), 0, PRODUCTS, 0, st), fl_conv)
-    cases["%-4s wino_wgrad" % tag] = (lambda al=al: al.cim_gemm_pair_batched(P(pV.buf), P(pD.buf), P(dU), 2 * C, C, NP, 2 * C, C, C, 1, 0, NPOS, pV.bs, pD.bs, 2 * C * C, P(pV.scale), P(pD.scale), 0, PRODUCTS, 0, st), fl_conv)
-    cases["%-4s fc1_fwd" % tag] = (lambda al=al: al.cim_gemm_pair(P(pX.buf), P(pW.buf), P(y1), None, N, 4096, K1, K1, K1, 4096, 0, 1, 0, sp(N, 4096, K1), P(ws), P(pX.scale), P(pW.scale), None, 0, PRODUCTS, 0, st), fl_fc)
-    cases["%-4s form1 wino_wgrad" % tag] = (lambda al=al: al.cim_gemm_pair_batched(P(pV.buf), P(pD.buf), P(dU), 2 * C, C, NP, 2 * C, C, C, 1, 0, NPOS, pV.bs, pD.bs, 2 * C * C, P(pV.scale), P(pD.scale), 0, PRODUCTS, 1, st), fl_conv)
-    cases["%-4s form1 fc1_wgrad" % tag] = (lambda al=al: al.cim_gemm_pair(P(pY.buf), P(pX.buf), P(dw1), None, 4096, K1, NP, 4096, K1, K1, 1, 0, 0, 1, None, P(pY.scale), P(pX.scale), None, 0, PRODUCTS, 1, st), fl_fc)
-    cases["%-4s fc1_dgrad" % tag] = (lambda al=al: al.cim_gemm_pair(P(pY.buf), P(pW.buf), P(dx1), None, N, K1, 4096, 4096, K1, K1, 0, 0, 0, 1, None, P(pY.scale), P(pW.scale), None, 0, PRODUCTS, 0, st), fl_fc)
-    cases["%-4s fc1_wgrad" % tag] = (lambda al=al: al.cim_gemm_pair(P(pY.buf), P(pX.buf), P(dw1), None, 4096, K1, NP, 4096, K1, K1, 1, 0, 0, 1, None, P(pY.scale), P(pX.scale), None, 0, PRODUCTS, 0, st), fl_fc)
+    pc, _ = product_cases(al)
+    for short in ALT_ROWS:
+        cases["%-4s %s" % (tag, short)] = pc[short]
 if not args.no_old:
     Vr, Vc = _amax(V, NP, 2 * C, 2 * C, True, True, NPOS, NP * 2 * C)
     _, Uc = _amax(U, 2 * C, C, C, False, True, NPOS, 2 * C * C)

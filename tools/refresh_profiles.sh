@@ -3,7 +3,8 @@
 #   bench line (with cpu_baseline and --phases), rocprofv3 kernel trace + stats of the same command (one row per GEMM PRODUCT),
 #   two --pmc passes for HBM traffic (separate runs) + their calibration passes, an SQ / GRBM pass for MFMA-busy and the
 #   wave-cycle split of the dominant GEMM and of the ROIAlign kernels, the GEMM ablation table, the other configurations,
-#   the micro-benchmarks.   Ablation builds: tools/build_alt.sh exp3|exp4|exp5 gemm_pair.hip -DCIM_PAIR_EXP=3|4|5 beforehand.
+#   the micro-benchmarks.   Ablation builds: tools/build_alt.sh exp3|exp4|exp5 gemm_pair.hip -DCIM_PAIR_EXP=3|4|5 beforehand
+#   (no LDS-DMA in the slab loop | MFMA only | both: the only values gemm_pair.hip accepts besides 0).
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/refresh
