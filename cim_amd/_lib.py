@@ -53,6 +53,7 @@ SIGNATURES = {
     "cim_bn_act_bwd_chunks": [c_int, c_int, c_int],
     "cim_bn_act_bwd": [_P, _P, _P, _P, _P, _P, c_float, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "cim_sgd_multi": [_P, _P, c_int, c_float, c_int, _P],
+    "cim_adam_multi": [_P, _P, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, _P],
     "cim_gemm_pair_splits": [c_int, c_int, c_int],
     "cim_gemm_pair": [_P, _P, _P, _P] + [c_int] * 6 + [c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, c_int, c_int, _P],
     "cim_gemm_pair_batched": [_P, _P, _P] + [c_int] * 6 + [c_int, c_int, c_int, c_longlong, c_longlong, c_longlong,

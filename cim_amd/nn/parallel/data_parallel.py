@@ -164,10 +164,10 @@ class DataParallel(nn.Module):
     def attach_optimizer(self, optimizer, early_modules=("Box_Head", "cls_iou_model")):
         """Let the wrapper start the optimizer step of the `early_modules`' parameters INSIDE the last backward pass of an
         optimizer step, as soon as their gradients are final (and, with several ranks, averaged): MaskFuse and the heads
-        hold 97 % of the parameter bytes and finish their backward first; their fused SGD update (HBM-bound, ~0.9 ms at
+        hold 97 % of the parameter bytes and finish their backward first; their fused update (HBM-bound, ~0.9 ms with SGD at
         cfg2) then runs on a side stream under the ROIAlign and backbone backward (latency-bound small launches).
         `optimizer.step()` stays where the driver calls it (tools/train.py:438) and updates the rest.
-        Needs cim_amd.optim.SGD (step_early); any other optimizer is left alone."""
+        Needs an optimizer with `step_early` (cim_amd.optim.SGD, cim_amd.optim.Adam); any other optimizer is left alone."""
         if not hasattr(optimizer, "step_early") or self.device.type != "cuda" or not engine.HAS_ENGINE_CALLBACK:
             return False
         params = []

@@ -3,10 +3,11 @@
 `param_groups` / `make_optimizer` restate /root/reference/tools/train.py:282-311 (two groups: weights, and biases with
 doubled learning rate and no weight decay; lr 0 until the schedule sets it); `LRSchedule.before_step` restates the
 warm-up and step-decay bookkeeping of tools/train.py:388-414.  The update itself is the fused HIP kernel behind
-`cim_amd.optim.SGD`.
+`cim_amd.optim.SGD` or, under SOLVER.TYPE Adam, `cim_amd.optim.Adam`.
 """
 from ..core.config import cfg
 from ..utils import net as net_utils
+from .adam import Adam
 from .sgd import SGD
 
 
@@ -23,9 +24,11 @@ def param_groups(model):
 
 
 def make_optimizer(model):
-    if cfg.SOLVER.TYPE != "SGD":
-        raise NotImplementedError("cim_amd.optim: SOLVER.TYPE %r - the shipped configs train with SGD" % (cfg.SOLVER.TYPE,))
-    return SGD(param_groups(model), momentum=cfg.SOLVER.MOMENTUM)
+    if cfg.SOLVER.TYPE == "SGD":
+        return SGD(param_groups(model), momentum=cfg.SOLVER.MOMENTUM)
+    if cfg.SOLVER.TYPE == "Adam":       # torch's defaults (betas 0.9 / 0.999, eps 1e-8), as train.py:311
+        return Adam(param_groups(model))
+    raise NotImplementedError("cim_amd.optim: SOLVER.TYPE %r - the reference's driver knows SGD and Adam" % (cfg.SOLVER.TYPE,))
 
 
 class LRSchedule:

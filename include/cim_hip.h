@@ -683,6 +683,32 @@ typedef struct cim_sgd_chunk {
 int cim_sgd_multi(const cim_sgd_tensor* tensors, const cim_sgd_chunk* chunks, int n_chunks, float momentum, int max_workgroups,
                   void* stream);
 
+/* Fused multi-tensor Adam (ABI-16 addition: cim_abi_version() stays 16): torch.optim.Adam's update with L2 weight decay
+ * (no amsgrad, no maximize) as constructed at tools/train.py:310-311, ONE launch for all tensors, in fp32:
+ *     g' = fma(wd, p, g)
+ *     m  = fma(beta1, m, (1 - beta1) * g')
+ *     v  = fma(beta2, v, (1 - beta2) * (g' * g'))
+ *     p  = p - (step_size * m) / (sqrt(v) / bc2_sqrt + eps)
+ * sqrt and both divisions are the correctly rounded fp32 operations.  beta1, beta2 and eps are doubles: beta and 1 - beta are
+ * each rounded to fp32 ONCE, from the double (1 - 0.999f is 1.3e-5 off 0.001: hundreds of ulps of every exp_avg_sq).
+ * step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) are per TENSOR (each has its own step count t) and
+ * computed by the caller in double precision.  Same two device tables, chunk meaning (16384-element flat chunks, 64 x 1024
+ * matrix tiles), max_workgroups walk and matrix-mode by-products (max |w_new| per row / column, the words cim_amax_rowcol
+ * produces) as cim_sgd_multi.  16-byte accesses are used when the four pointers of a tensor are 16-byte aligned. */
+typedef struct cim_adam_tensor {
+    uint64_t p;            /* float* parameter (device address) */
+    uint64_t g;            /* const float* gradient */
+    uint64_t exp_avg;      /* float* first moment m (zero-initialised by the caller) */
+    uint64_t exp_avg_sq;   /* float* second moment v (zero-initialised by the caller) */
+    int64_t n;             /* elements */
+    float step_size, bc2_sqrt, wd;
+    int32_t rows, cols;    /* matrix mode when cols > 0: see cim_sgd_tensor */
+    int32_t reserved;      /* 0 */
+    uint64_t row_amax, col_amax;
+} cim_adam_tensor;         /* 80 bytes */
+int cim_adam_multi(const cim_adam_tensor* tensors, const cim_sgd_chunk* chunks, int n_chunks, double beta1, double beta2, double eps,
+                   int max_workgroups, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
