@@ -14,6 +14,25 @@ struct W7 {
     static constexpr int QOFF[4] = {0, 36, 66, 96};   // first position of tile type ka * 2 + kb (121 in total)
 };
 
+// A tile type as a compile-time pair, and the ONE dispatch from a runtime tile type t = ka * 2 + kb (QOFF's index: a grid index,
+// a wave index) to it: f(W7Type<KA, KB>{}) with f a generic always-inline lambda, so that each call site inlines four bodies.
+template <int KA_, int KB_> struct W7Type { static constexpr int KA = KA_, KB = KB_; };
+template <typename F> __device__ __forceinline__ void w7_for_tile(int t, F&& f) {
+    switch (t) {
+        case 0: f(W7Type<0, 0>{}); break;
+        case 1: f(W7Type<0, 1>{}); break;
+        case 2: f(W7Type<1, 0>{}); break;
+        default: f(W7Type<1, 1>{}); break;
+    }
+}
+// all four tile types, in position order
+template <typename F> __device__ __forceinline__ void w7_for_all_tiles(F&& f) {
+    f(W7Type<0, 0>{});
+    f(W7Type<0, 1>{});
+    f(W7Type<1, 0>{});
+    f(W7Type<1, 1>{});
+}
+
 __device__ __forceinline__ void fma4(float4& a, float s, float4 v) {
     a.x = fmaf(s, v.x, a.x); a.y = fmaf(s, v.y, a.y); a.z = fmaf(s, v.z, a.z); a.w = fmaf(s, v.w, a.w);
 }

@@ -1,15 +1,22 @@
 // Winograd-domain stages of the MaskFuse 3 x 3 convolution on R x 7 x 7 ROI maps in the MIXED 4 + 3 tiling, and the (c, h, w)
 // flatten in front of seg_fc.0 - the producers and consumers of the pair engine's operands (gemm_pair.hip).
 //
-// Replaces (together with cim_gemm_pair_batched) the evaluation of nn.Conv2d(2C, C, 3, padding=1) of
-// /root/reference/lib/modeling/resnet50.py:104 and its two gradients:
+// Replaces (together with cim_gemm_pair_batched) the evaluation of nn.Conv2d(2C, C, 3, padding=1) of the reference's
+// lib/modeling/resnet50.py:104 and its two gradients:
 //   forward        :  y  = A^T [ (G g G^T) . (B^T d B) ] A          per tile (Lavin & Gray), 121 multiplies per 49 outputs
 //   data gradient  :  dx = overlap-add of B [ (A dy A^T) . U^T ] B^T   (the ADJOINT of the forward: reuses the forward's U)
 //   weight gradient:  dW = AW [ (B^T d B)^T . (GD dy GD^T) ] AW^T
 // Layouts: activations channels-last [R,7,7,C]; transformed operands position-major, [121][rows][C], as pair images (written by
 // the transforms here, or by csrc/roi_align.hip's fused forward); GEMM results fp32.  HBM-bound kernels: lanes along C, 16 bytes
-// per lane.  The superseded F(2x2,3x3) / F(4x4,3x3) algorithms and the fp32 / bf16x3 / f16x2 engines they fed are test
-// infrastructure (experiments/csrc/winograd_all.hip, round 5).
+// per lane where the tile fits the register file.  Kernels:
+//   forward   wino7_input_pair (x -> V'), wino7_filter_pair (w -> U'), wino7_output (M -> y, max |y|)
+//   backward  wino7_dy_pair<ADJ> (dy -> E' | D'), wino7_flatten_bwd_dy_pair (flatten backward + ReLU mask + both of those),
+//             wino7_dx (Md -> dx), wino7_dx_maskfold (Md -> dbox), wino7_wgrad_out_rows / wino7_wgrad_out (dU -> dW)
+//   scales    wino7_pair_scales;   flatten   flatten_chw_pair (y -> X'), flatten_chw_bwd (dX -> dy, bias partial sums)
+// Each stage's arithmetic is written once, per tile type (KA, KB); w7_for_tile / w7_for_all_tiles (wino7_tile.h) are the only
+// dispatch over tile types.  No build switch selects code here: the lane widths and wave counts below are the measured choices
+// (their alternatives were last in the tree at commit 55ec0cf).  The superseded F(2x2,3x3) / F(4x4,3x3) algorithms and the
+// fp32 / bf16x3 / f16x2 engines they fed are test infrastructure (experiments/csrc/winograd_all.hip, round 5).
 #include "common.h"
 #include "../../include/cim_hip.h"
 #include "wino7_tile.h"
@@ -17,7 +24,6 @@
 namespace {
 
 __device__ __forceinline__ float4 f4(float v) { return make_float4(v, v, v, v); }
-__device__ __forceinline__ float2 f2(float v) { return make_float2(v, v); }
 __device__ __forceinline__ void fma2(float2& a, float s, float2 v) { a.x = fmaf(s, v.x, a.x); a.y = fmaf(s, v.y, a.y); }
 
 // =============================================================================================
@@ -28,138 +34,54 @@ __device__ __forceinline__ void fma2(float2& a, float s, float2 v) { a.x = fmaf(
 // contractions, and V / D / M shrink by the same factor).  `tile == 7` in the C entry points; P must be 7.
 // Matrices (wino43_mats.h, W7_*: [axis kind][..][..], zero padded): B^T, G, A^T; weight gradient: GD (dy transform), AW.
 // Layouts: V, D, M: [121][R][C];  U, dU: [121][K][N].
-#ifndef CIM_W7_NT
-#define CIM_W7_NT 1             // 1 = nontemporal stores of the transform outputs (streamed once, consumed by the next kernel)
-#endif
 typedef float w7_v2 __attribute__((ext_vector_type(2)));
 typedef float w7_v4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void w7_store(float* p, float v) {
-#if CIM_W7_NT
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-__device__ __forceinline__ void w7_store(float* p, float2 v) {
-#if CIM_W7_NT
-    __builtin_nontemporal_store(w7_v2{v.x, v.y}, reinterpret_cast<w7_v2*>(p));
-#else
-    *reinterpret_cast<float2*>(p) = v;
-#endif
-}
-__device__ __forceinline__ void w7_store(float* p, float4 v) {
-#if CIM_W7_NT
-    __builtin_nontemporal_store(w7_v4{v.x, v.y, v.z, v.w}, reinterpret_cast<w7_v4*>(p));
-#else
-    *reinterpret_cast<float4*>(p) = v;
-#endif
-}
 
-// pair-image output: w7_store_pair of wino7_tile.h
-__device__ __forceinline__ void w7_store_pair(float*, const float2&, float) {}      // (only 4-channel lanes write pair images)
-__device__ __forceinline__ void w7_store_pair(float*, float, float) {}
+// Channels per lane of the fp32-side kernels: 16-byte accesses stream at 6.6-6.8 TB/s where the 4- / 8-byte ones reach 4.3-5.0
+// (tools/bench_wino.py), as long as the tile still fits the register file.
+constexpr int W7_VOUT = 4;      // output transform M -> y: the 4 x 6 row sums fit (204 VGPRs)
+constexpr int W7_VDX = 2;       // adjoint output Md -> dx: 49 accumulators per channel, two per lane fill the file (256 VGPRs)
+constexpr int W7_VMF = 1;       // mask-folding adjoint output Md -> dbox: two per lane need 314 VGPRs (0.266 vs 0.235 ms at cfg2)
+constexpr int W7_MF_WAVES = 1;  // ... and its register cap: waves per SIMD the compiler must allow
+constexpr int W7_FB_WAVES = 3;  // the fused flatten-backward kernel: three workgroups per CU is what its 54032 B of LDS allow
+constexpr int W7_WG_CI = 4;     // ci rows per workgroup of wino7_wgrad_out_rows_kernel: 144-byte store runs per co row
 
-// lane vector width of the transform kernels (channels per lane): 16-byte accesses stream at 6.6-6.8 TB/s where the
-// 4- / 8-byte ones reach 4.3-5.0 (tools/bench_wino.py), as long as the tile still fits the register file
-#ifndef CIM_W7_VIN
-#define CIM_W7_VIN 4            // input transform  x -> V      (2 | 4)
-#endif
-#ifndef CIM_W7_VOUT
-#define CIM_W7_VOUT 4           // output transform M -> y      (2 | 4)
-#endif
-#ifndef CIM_W7_VMF
-#define CIM_W7_VMF 1            // mask-folding adjoint output   Md -> dbox    (1 | 2): one channel per lane keeps both halves'
-                                // transforms at ~120 VGPRs (two per lane: 314, one wave per SIMD - 0.266 vs 0.235 ms at cfg2)
-#endif
-#ifndef CIM_W7_MF_WAVES
-#define CIM_W7_MF_WAVES 1       // register cap of that kernel: waves per SIMD the compiler must allow
-#endif
-#ifndef CIM_W7_VDX
-#define CIM_W7_VDX 2            // adjoint output   Md -> dx    (1 | 2 | 4)
-#endif
-#ifndef CIM_W7_VWG
-#define CIM_W7_VWG 1            // weight-gradient output dU -> dW (1 | 4; measured 0.254 | 0.297 ms)
-#endif
+// lane vectors of 1 / 2 / 4 channels.  Transform outputs are streamed once and consumed by the next kernel: nontemporal stores;
+// vload_once: nontemporal loads of the inputs that are read exactly once (M, Md, dU, dX).
 template <int N> struct w7_vec;
 template <> struct w7_vec<1> { typedef float T; };
 template <> struct w7_vec<2> { typedef float2 T; };
 template <> struct w7_vec<4> { typedef float4 T; };
+__device__ __forceinline__ void w7_store(float* p, float v) { __builtin_nontemporal_store(v, p); }
+__device__ __forceinline__ void w7_store(float* p, float2 v) { __builtin_nontemporal_store(w7_v2{v.x, v.y}, reinterpret_cast<w7_v2*>(p)); }
+__device__ __forceinline__ void w7_store(float* p, float4 v) {
+    __builtin_nontemporal_store(w7_v4{v.x, v.y, v.z, v.w}, reinterpret_cast<w7_v4*>(p));
+}
 __device__ __forceinline__ void vzero(float& a) { a = 0.0f; }
 __device__ __forceinline__ void vzero(float2& a) { a = make_float2(0.f, 0.f); }
 __device__ __forceinline__ void vzero(float4& a) { a = make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ void vfma(float& a, float s, float v) { a = fmaf(s, v, a); }
 __device__ __forceinline__ void vfma(float2& a, float s, float2 v) { fma2(a, s, v); }
 __device__ __forceinline__ void vfma(float4& a, float s, float4 v) { fma4(a, s, v); }
-__device__ __forceinline__ float vamax(float v) { return fabsf(v); }
-__device__ __forceinline__ float vamax(float2 v) { return fmaxf(fabsf(v.x), fabsf(v.y)); }
 __device__ __forceinline__ float vamax(float4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
-__device__ __forceinline__ void vrelu(float& v) { v = fmaxf(v, 0.f); }
-__device__ __forceinline__ void vrelu(float2& v) { v = make_float2(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f)); }
 __device__ __forceinline__ void vrelu(float4& v) { v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)); }
-__device__ __forceinline__ float vget(float v, int) { return v; }
-__device__ __forceinline__ float vget(const float4& v, int l) { return l == 0 ? v.x : l == 1 ? v.y : l == 2 ? v.z : v.w; }
 template <typename T> __device__ __forceinline__ T vload(const float* p) { return *reinterpret_cast<const T*>(p); }
-#ifndef CIM_W7_NTL
-#define CIM_W7_NTL 1            // 1 = nontemporal loads of the transform inputs that are read exactly once (M, Md, dU)
-#endif
 template <typename T> __device__ __forceinline__ T vload_once(const float* p) {
-#if CIM_W7_NTL
     if constexpr (sizeof(T) == 4) return __builtin_nontemporal_load(p);
     else if constexpr (sizeof(T) == 8) { const w7_v2 v = __builtin_nontemporal_load(reinterpret_cast<const w7_v2*>(p)); return make_float2(v.x, v.y); }
     else { const w7_v4 v = __builtin_nontemporal_load(reinterpret_cast<const w7_v4*>(p)); return make_float4(v.x, v.y, v.z, v.w); }
-#else
-    return vload<T>(p);
-#endif
 }
 
-__host__ __device__ constexpr float w7_abs_row_sum(const float (&M)[6], int n) {
-    float s = 0.0f;
-    for (int k = 0; k < n; ++k) s += M[k] < 0 ? -M[k] : M[k];
-    return s;
-}
-
-// x [R][7][7][C] fp32 -> tile type (KA, KB) of the pair image V [121][R (position stride, padded)][C], scale [121]
-template <int KA, int KB, bool AMAX>
-__device__ __forceinline__ void w7_input_tile(const float* __restrict__ x, float* __restrict__ V, int r, int R, int C,
-                                              unsigned* __restrict__ row_amax, const float* __restrict__ scale) {
-    constexpr int NA = W7::NP[KA], NB = W7::NP[KB], P = 7, Q0 = W7::QOFF[KA * 2 + KB];
-    float dmax = 0.0f;
-    for (int c = threadIdx.x * 4; c < C; c += 256 * 4)
-        w7_input_tile_regs<KA, KB>(
-            [&](int iy, int ix) {
-                const float4 v = vload<float4>(x + (((size_t)r * P + iy) * P + ix) * C + c);
-                if constexpr (AMAX) dmax = fmaxf(dmax, vamax(v));
-                return v;
-            },
-            V, (size_t)R * C, (size_t)r * C + c, scale);
-    if constexpr (AMAX) {       // row-scale bounds of this tile's positions (see wino43_input_kernel)
-        __shared__ float red[4];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, o));
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = dmax;
-        __syncthreads();
-        if (threadIdx.x < NA * NB) {
-            const float tile_max = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-            const int i = threadIdx.x / NB, j = threadIdx.x % NB;
-            float fi = 0.0f, fj = 0.0f;
-#pragma unroll
-            for (int p = 0; p < 6; ++p) {
-                if (p == i) fi = w7_abs_row_sum(W7_BT[KA][p], NA);
-                if (p == j) fj = w7_abs_row_sum(W7_BT[KB][p], NB);
-            }
-            row_amax[(size_t)(Q0 + threadIdx.x) * R + r] = __float_as_uint(fi * fj * tile_max * 1.0001f);
-        }
-    }
-}
-
-// zero rows of a pair image: positions [q0, q0 + nq) of row r (the rows that pad R up to a multiple of 32)
+// zero rows of a pair image: positions [q0, q0 + nq) of row r (the rows that pad R up to a multiple of 32).  (The fused
+// flatten-backward kernel zeroes its own: a 256-channel slice of all 121 positions, wave-strided nontemporal stores.)
 __device__ __forceinline__ void w7_zero_rows(float* __restrict__ V, int q0, int nq, int r, int Rs, int C) {
     for (int q = q0; q < q0 + nq; ++q)
         for (int c = threadIdx.x * 4; c < C; c += 1024)
             *reinterpret_cast<float4*>(V + ((size_t)q * Rs + r) * C + c) = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// x [R][7][7][C] fp32 -> pair image V [121][Rs][C] (Rs = R padded to 32 rows, pad rows zeroed); grid = (Rs, 4)
+// x [R][7][7][C] fp32 -> pair image V [121][Rs][C] (Rs = R padded to 32 rows, pad rows zeroed); grid = (Rs, 4 tile types).
+// The tile transform B^T d B and the pair store are wino7_tile.h's (shared with roi_align.hip's fused forward).
 __global__ __launch_bounds__(256) void wino7_input_pair_kernel(const float* __restrict__ x, float* __restrict__ V, int R, int Rs,
                                                                int C, const float* __restrict__ scale) {
     const int r = blockIdx.x;
@@ -167,12 +89,11 @@ __global__ __launch_bounds__(256) void wino7_input_pair_kernel(const float* __re
         w7_zero_rows(V, W7::QOFF[blockIdx.y], W7::NP[blockIdx.y >> 1] * W7::NP[blockIdx.y & 1], r, Rs, C);
         return;
     }
-    switch (blockIdx.y) {
-        case 0: w7_input_tile<0, 0, false>(x, V, r, Rs, C, nullptr, scale); break;
-        case 1: w7_input_tile<0, 1, false>(x, V, r, Rs, C, nullptr, scale); break;
-        case 2: w7_input_tile<1, 0, false>(x, V, r, Rs, C, nullptr, scale); break;
-        default: w7_input_tile<1, 1, false>(x, V, r, Rs, C, nullptr, scale); break;
-    }
+    w7_for_tile(blockIdx.y, [&](auto t) __attribute__((always_inline)) {
+        for (int c = threadIdx.x * 4; c < C; c += 256 * 4)
+            w7_input_tile_regs<t.KA, t.KB>([&](int iy, int ix) { return vload<float4>(x + (((size_t)r * 7 + iy) * 7 + ix) * C + c); },
+                                           V, (size_t)Rs * C, (size_t)r * C + c, scale);
+    });
 }
 
 // Filter transform into a pair image U' [121][Cout][Cin] (ci contiguous: the B operand of the forward product read
@@ -219,10 +140,9 @@ __global__ __launch_bounds__(256) void wino7_filter_pair_kernel(const float* __r
     const int lane = threadIdx.x & 63, j = lane & 7;
     const int src_a = ((lane & ~7) + 2 * (j & 3)) * 4, src_b = src_a + 4;
     if (!live) return;               // (KN is a multiple of 8 and idx is chunk-aligned per 8 lanes: whole chunks leave together)
-    w7_filter_pair_tile<0, 0>(w, U, KN, idx, scale, src_a, src_b, j < 4);
-    w7_filter_pair_tile<0, 1>(w, U, KN, idx, scale, src_a, src_b, j < 4);
-    w7_filter_pair_tile<1, 0>(w, U, KN, idx, scale, src_a, src_b, j < 4);
-    w7_filter_pair_tile<1, 1>(w, U, KN, idx, scale, src_a, src_b, j < 4);
+    w7_for_all_tiles([&](auto t) __attribute__((always_inline)) {
+        w7_filter_pair_tile<t.KA, t.KB>(w, U, KN, idx, scale, src_a, src_b, j < 4);
+    });
 }
 
 template <int KA, int KB, int VW>
@@ -271,12 +191,9 @@ __global__ __launch_bounds__(256) void wino7_output_kernel(const float* __restri
                                                            unsigned* __restrict__ y_amax) {
     const int r = blockIdx.x;
     float ymax = 0.0f;
-    switch (blockIdx.y) {
-        case 0: w7_output_tile<0, 0, CIM_W7_VOUT>(M, bias, y, r, R, C, relu, ymax); break;
-        case 1: w7_output_tile<0, 1, CIM_W7_VOUT>(M, bias, y, r, R, C, relu, ymax); break;
-        case 2: w7_output_tile<1, 0, CIM_W7_VOUT>(M, bias, y, r, R, C, relu, ymax); break;
-        default: w7_output_tile<1, 1, CIM_W7_VOUT>(M, bias, y, r, R, C, relu, ymax); break;
-    }
+    w7_for_tile(blockIdx.y, [&](auto t) __attribute__((always_inline)) {
+        w7_output_tile<t.KA, t.KB, W7_VOUT>(M, bias, y, r, R, C, relu, ymax);
+    });
     if (y_amax != nullptr) {             // (one atomicMax per workgroup: see pair_masked_stats_kernel)
         __shared__ float s_ymax[4];
 #pragma unroll
@@ -288,108 +205,15 @@ __global__ __launch_bounds__(256) void wino7_output_kernel(const float* __restri
     }
 }
 
-// Output-gradient tile transform.  ADJ = false: D = GD dy GD^T (weight gradient, F(3,4) / F(3,3)).
+// Output-gradient tile transform of the lane's 4 channels, d [OA][OB] in registers -> pair image positions Q0 .. Q0 + NA NB of D
+// (position stride MC floats) at element offset rc; scale [121].  ADJ = false: D = GD dy GD^T (weight gradient, F(3,4) / F(3,3)).
 // ADJ = true: E = A dy A^T with A = (A^T)^T - the first stage of the data gradient written as the ADJOINT of the forward,
 //   y = A^T [U . (B^T d B)] A   =>   dx (+)= B [U^T . (A dy A^T)] B^T      (overlap-add over the tiles' patches),
-// which reuses the forward's U (contracted over the other channel index) instead of transforming a rotated filter;
-// with AMAX it also stores the row-scale bounds of E (column abs sums of A^T times the tile's max |dy|).
-template <int KA, int KB, bool ADJ, bool AMAX, bool PAIR = false>
-__device__ __forceinline__ void w7_dy_tile(const float* __restrict__ dy, float* __restrict__ D, int r, int R, int C,
-                                           unsigned* __restrict__ row_amax, const float* __restrict__ scale = nullptr) {
-    constexpr int NA = W7::NP[KA], NB = W7::NP[KB], OA = W7::OUT[KA], OB = W7::OUT[KB], P = 7, Q0 = W7::QOFF[KA * 2 + KB];
-    const size_t MC = (size_t)R * C;
-    float dmax = 0.0f;
-    for (int c = threadIdx.x * 4; c < C; c += 256 * 4) {      // 16 B per lane: the 4 x 4 tile fits the register budget
-        float4 d[OA][OB];
-#pragma unroll
-        for (int a = 0; a < OA; ++a)
-#pragma unroll
-            for (int b = 0; b < OB; ++b) {
-                d[a][b] = *reinterpret_cast<const float4*>(dy + (((size_t)r * P + W7::OUT0[KA] + a) * P + W7::OUT0[KB] + b) * C + c);
-                if constexpr (AMAX)
-                    dmax = fmaxf(dmax, fmaxf(fmaxf(fabsf(d[a][b].x), fabsf(d[a][b].y)), fmaxf(fabsf(d[a][b].z), fabsf(d[a][b].w))));
-            }
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            float4 trow[OB];
-#pragma unroll
-            for (int b = 0; b < OB; ++b) {
-                trow[b] = f4(0.f);
-#pragma unroll
-                for (int a = 0; a < OA; ++a) {
-                    const float m = ADJ ? W7_AT[KA][a][i] : W7_GD[KA][i][a];
-                    if (m != 0.0f) fma4(trow[b], m, d[a][b]);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                float4 v = f4(0.f);
-#pragma unroll
-                for (int b = 0; b < OB; ++b) {
-                    const float m = ADJ ? W7_AT[KB][b][j] : W7_GD[KB][j][b];
-                    if (m != 0.0f) fma4(v, m, trow[b]);
-                }
-                if constexpr (PAIR) w7_store_pair(D + (size_t)(Q0 + i * NB + j) * MC + (size_t)r * C + c, v, scale[Q0 + i * NB + j]);
-                else w7_store(D + (size_t)(Q0 + i * NB + j) * MC + (size_t)r * C + c, v);
-            }
-        }
-    }
-    if constexpr (AMAX) {
-        __shared__ float red[4];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, o));
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = dmax;
-        __syncthreads();
-        if (threadIdx.x < NA * NB) {
-            const float tile_max = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-            const int i = threadIdx.x / NB, j = threadIdx.x % NB;
-            float fi = 0.0f, fj = 0.0f;
-#pragma unroll
-            for (int p = 0; p < 6; ++p) {
-                float sa = 0.0f, sb = 0.0f;
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    sa += fabsf(ADJ ? W7_AT[KA][a][p] : W7_GD[KA][p][a]);
-                    sb += fabsf(ADJ ? W7_AT[KB][a][p] : W7_GD[KB][p][a]);
-                }
-                if (p == i) fi = sa;
-                if (p == j) fj = sb;
-            }
-            row_amax[(size_t)(Q0 + threadIdx.x) * R + r] = __float_as_uint(fi * fj * tile_max * 1.0001f);
-        }
-    }
-}
-
-// dy [R][7][7][C] fp32 -> pair image D / E [121][Rs][C]; grid = (Rs, 4)
-template <bool ADJ>
-__global__ __launch_bounds__(256) void wino7_dy_pair_kernel(const float* __restrict__ dy, float* __restrict__ D, int R, int Rs,
-                                                            int C, const float* __restrict__ scale) {
-    const int r = blockIdx.x;
-    if (r >= R) {
-        w7_zero_rows(D, W7::QOFF[blockIdx.y], W7::NP[blockIdx.y >> 1] * W7::NP[blockIdx.y & 1], r, Rs, C);
-        return;
-    }
-    switch (blockIdx.y) {
-        case 0: w7_dy_tile<0, 0, ADJ, false, true>(dy, D, r, Rs, C, nullptr, scale); break;
-        case 1: w7_dy_tile<0, 1, ADJ, false, true>(dy, D, r, Rs, C, nullptr, scale); break;
-        case 2: w7_dy_tile<1, 0, ADJ, false, true>(dy, D, r, Rs, C, nullptr, scale); break;
-        default: w7_dy_tile<1, 1, ADJ, false, true>(dy, D, r, Rs, C, nullptr, scale); break;
-    }
-}
-
-// ---- flatten backward + ReLU mask + BOTH output-gradient transforms of the convolution in one launch -------------------------------
-// Replaces flatten_chw_kernel<false> + wino7_dy_pair_kernel<true> + wino7_dy_pair_kernel<false> (the backward of `.view(N, -1)`
-// and mask_branch's ReLU, /root/reference/lib/modeling/resnet50.py:135,104-105, in front of the convolution's two gradient products):
-// dX [R][C * 49] ((c, h, w) order, seg_fc.0's data gradient) is read ONCE, masked with the saved conv output, and leaves as the
-// pair images E = A dy A^T (adjoint data gradient) and D = GD dy GD^T (weight gradient) - the masked gradient dy [R,7,7,C] is
-// never stored (was: 200 MB written, read twice).  Workgroup = (ROI, 256-channel slice): the slice's 49 x 256 gradients are 12544
-// CONSECUTIVE floats of dX; they are transposed through LDS ([49][260] floats), masked in place (a lane owns 4 channels, a wave
-// every fourth pixel: the bias partial sums keep flatten_chw_kernel's order), then wave t transforms tile type t from LDS exactly as
-// w7_dy_tile does from memory - bit-identical images.  grid = (Rs, C / 256); rows R .. Rs-1 are zeroed.
-constexpr int W7_FB_LDW = 260;
-
+// which reuses the forward's U (contracted over the other channel index) instead of transforming a rotated filter.
+// The ONE copy of this arithmetic: wino7_dy_pair_kernel (d from global memory) and the fused flatten-backward kernel (d from its
+// LDS tile) both call it, which is why their images agree bit for bit.
 template <int KA, int KB, bool ADJ>
-__device__ __forceinline__ void w7_dy_regs_pair(const float4 (&d)[W7::OUT[KA]][W7::OUT[KB]], float* __restrict__ D, size_t MC, size_t rc,
+__device__ __forceinline__ void w7_dy_tile_regs(const float4 (&d)[W7::OUT[KA]][W7::OUT[KB]], float* __restrict__ D, size_t MC, size_t rc,
                                                 const float* __restrict__ scale) {
     constexpr int NA = W7::NP[KA], NB = W7::NP[KB], OA = W7::OUT[KA], OB = W7::OUT[KB], Q0 = W7::QOFF[KA * 2 + KB];
 #pragma unroll
@@ -417,9 +241,43 @@ __device__ __forceinline__ void w7_dy_regs_pair(const float4 (&d)[W7::OUT[KA]][W
     }
 }
 
-template <int KA, int KB>
-__device__ __forceinline__ void w7_fb_tile(const float* __restrict__ s, int lane, float* __restrict__ E, float* __restrict__ D, size_t MC,
-                                           size_t rc, const float* __restrict__ sE, const float* __restrict__ sD) {
+// dy [R][7][7][C] fp32 -> pair image D / E [121][Rs][C]; grid = (Rs, 4 tile types)
+template <bool ADJ>
+__global__ __launch_bounds__(256) void wino7_dy_pair_kernel(const float* __restrict__ dy, float* __restrict__ D, int R, int Rs,
+                                                            int C, const float* __restrict__ scale) {
+    const int r = blockIdx.x;
+    if (r >= R) {
+        w7_zero_rows(D, W7::QOFF[blockIdx.y], W7::NP[blockIdx.y >> 1] * W7::NP[blockIdx.y & 1], r, Rs, C);
+        return;
+    }
+    w7_for_tile(blockIdx.y, [&](auto t) __attribute__((always_inline)) {
+        constexpr int KA = t.KA, KB = t.KB, OA = W7::OUT[KA], OB = W7::OUT[KB];
+        for (int c = threadIdx.x * 4; c < C; c += 256 * 4) {      // 16 B per lane: the 4 x 4 tile fits the register budget
+            float4 d[OA][OB];
+#pragma unroll
+            for (int a = 0; a < OA; ++a)
+#pragma unroll
+                for (int b = 0; b < OB; ++b)
+                    d[a][b] = vload<float4>(dy + (((size_t)r * 7 + W7::OUT0[KA] + a) * 7 + W7::OUT0[KB] + b) * C + c);
+            w7_dy_tile_regs<KA, KB, ADJ>(d, D, (size_t)Rs * C, (size_t)r * C + c, scale);
+        }
+    });
+}
+
+// ---- flatten backward + ReLU mask + BOTH output-gradient transforms of the convolution in one launch -------------------------------
+// Replaces flatten_chw_bwd_kernel + wino7_dy_pair_kernel<true> + wino7_dy_pair_kernel<false> (the backward of `.view(N, -1)` and
+// mask_branch's ReLU, the reference's lib/modeling/resnet50.py:135,104-105, in front of the convolution's two gradient products):
+// dX [R][C * 49] ((c, h, w) order, seg_fc.0's data gradient) is read ONCE, masked with the saved conv output, and leaves as the
+// pair images E = A dy A^T (adjoint data gradient) and D = GD dy GD^T (weight gradient) - the masked gradient dy [R,7,7,C] is
+// never stored (was: 200 MB written, read twice).  Workgroup = (ROI, 256-channel slice): the slice's 49 x 256 gradients are 12544
+// CONSECUTIVE floats of dX; they are transposed through LDS ([49][260] floats), masked in place (a lane owns 4 channels, a wave
+// every fourth pixel: the bias partial sums keep flatten_chw_bwd_kernel's order), then wave t transforms tile type t from LDS with
+// w7_dy_tile_regs - bit-identical images.  grid = (Rs, C / 256); rows R .. Rs-1 are zeroed.
+constexpr int W7_FB_LDW = 260;
+
+template <int KA, int KB, bool ADJ>
+__device__ __forceinline__ void w7_fb_tile(const float* __restrict__ s, int lane, float* __restrict__ img, size_t MC, size_t rc,
+                                           const float* __restrict__ scale) {
     constexpr int OA = W7::OUT[KA], OB = W7::OUT[KB];
     float4 d[OA][OB];
 #pragma unroll
@@ -427,14 +285,10 @@ __device__ __forceinline__ void w7_fb_tile(const float* __restrict__ s, int lane
 #pragma unroll
         for (int b = 0; b < OB; ++b)
             d[a][b] = *reinterpret_cast<const float4*>(s + ((W7::OUT0[KA] + a) * 7 + W7::OUT0[KB] + b) * W7_FB_LDW + 4 * lane);
-    if (E != nullptr) w7_dy_regs_pair<KA, KB, true>(d, E, MC, rc, sE);
-    if (D != nullptr) w7_dy_regs_pair<KA, KB, false>(d, D, MC, rc, sD);
+    if (img != nullptr) w7_dy_tile_regs<KA, KB, ADJ>(d, img, MC, rc, scale);
 }
 
-#ifndef CIM_W7_FB_WAVES
-#define CIM_W7_FB_WAVES 3
-#endif
-__global__ __launch_bounds__(256, CIM_W7_FB_WAVES) void wino7_flatten_bwd_dy_pair_kernel(const float* __restrict__ dX, const float* __restrict__ y,
+__global__ __launch_bounds__(256, W7_FB_WAVES) void wino7_flatten_bwd_dy_pair_kernel(const float* __restrict__ dX, const float* __restrict__ y,
                                                                         float* __restrict__ E, float* __restrict__ D,
                                                                         float* __restrict__ bsum, int R, int Rs, int C,
                                                                         const float* __restrict__ sE, const float* __restrict__ sD) {
@@ -488,12 +342,10 @@ __global__ __launch_bounds__(256, CIM_W7_FB_WAVES) void wino7_flatten_bwd_dy_pai
     }
     // wave t: the adjoint image of tile type t and the weight-gradient image of tile type 3 - t (36 + 25, 30 + 30, 30 + 30, 25 + 36
     // positions: the four waves carry the same number of stores)
-    switch (w) {
-        case 0: w7_fb_tile<0, 0>(s, lane, E, nullptr, MC, rc, sE, sD); w7_fb_tile<1, 1>(s, lane, nullptr, D, MC, rc, sE, sD); break;
-        case 1: w7_fb_tile<0, 1>(s, lane, E, nullptr, MC, rc, sE, sD); w7_fb_tile<1, 0>(s, lane, nullptr, D, MC, rc, sE, sD); break;
-        case 2: w7_fb_tile<1, 0>(s, lane, E, nullptr, MC, rc, sE, sD); w7_fb_tile<0, 1>(s, lane, nullptr, D, MC, rc, sE, sD); break;
-        default: w7_fb_tile<1, 1>(s, lane, E, nullptr, MC, rc, sE, sD); w7_fb_tile<0, 0>(s, lane, nullptr, D, MC, rc, sE, sD); break;
-    }
+    w7_for_tile(w, [&](auto t) __attribute__((always_inline)) {
+        w7_fb_tile<t.KA, t.KB, true>(s, lane, E, MC, rc, sE);
+        w7_fb_tile<1 - t.KA, 1 - t.KB, false>(s, lane, D, MC, rc, sD);
+    });
 }
 
 // scale[q] = 2^(14 - exponent(bound_q)), bound_q = (abs row sum)_i (abs row sum)_j max|d| 1.0001 >= max |transformed value| at
@@ -556,9 +408,9 @@ __device__ __forceinline__ void w7_dx_tile(const float* __restrict__ M, size_t M
     }
 }
 
-// grid = (R, channel chunks); block = 256 (CIM_W7_VDX channels per lane)
+// grid = (R, channel chunks); block = 256 (W7_VDX channels per lane)
 __global__ __launch_bounds__(256) void wino7_dx_kernel(const float* __restrict__ M, float* __restrict__ dx, int R, int C) {
-    constexpr int VW = CIM_W7_VDX;
+    constexpr int VW = W7_VDX;
     typedef typename w7_vec<VW>::T VT;
     const int r = blockIdx.x;
     const size_t MC = (size_t)R * C;
@@ -569,10 +421,7 @@ __global__ __launch_bounds__(256) void wino7_dx_kernel(const float* __restrict__
 #pragma unroll
             for (int x = 0; x < 7; ++x) vzero(acc[y][x]);
         const size_t rc = (size_t)r * C + c;
-        w7_dx_tile<0, 0, VT>(M, MC, rc, acc);
-        w7_dx_tile<0, 1, VT>(M, MC, rc, acc);
-        w7_dx_tile<1, 0, VT>(M, MC, rc, acc);
-        w7_dx_tile<1, 1, VT>(M, MC, rc, acc);
+        w7_for_all_tiles([&](auto t) __attribute__((always_inline)) { w7_dx_tile<t.KA, t.KB, VT>(M, MC, rc, acc); });
 #pragma unroll
         for (int y = 0; y < 7; ++y)
 #pragma unroll
@@ -585,9 +434,9 @@ __global__ __launch_bounds__(256) void wino7_dx_kernel(const float* __restrict__
 // A lane transforms channel c of the MASKED half first (all four tile types into the 49 accumulators), scales by the ROI's 7 x 7
 // mask, then accumulates the plain half on top: dbox [R,7,7,Cb] is written instead of dcat [R,7,7,2Cb] - half the bytes out of
 // this launch and half the bytes into the ROIAlign backward (which re-reads them 1.5x).  grid = (R, chunks); block = 256.
-__global__ __launch_bounds__(256, CIM_W7_MF_WAVES) void wino7_dx_maskfold_kernel(const float* __restrict__ M, const float* __restrict__ masks,
+__global__ __launch_bounds__(256, W7_MF_WAVES) void wino7_dx_maskfold_kernel(const float* __restrict__ M, const float* __restrict__ masks,
                                                                 float* __restrict__ dbox, int R, int Cb) {
-    constexpr int VW = CIM_W7_VMF;
+    constexpr int VW = W7_VMF;
     typedef typename w7_vec<VW>::T VT;
     const int r = blockIdx.x;
     const size_t C2 = 2 * (size_t)Cb, MC = (size_t)R * C2;
@@ -599,10 +448,7 @@ __global__ __launch_bounds__(256, CIM_W7_MF_WAVES) void wino7_dx_maskfold_kernel
 #pragma unroll
             for (int x = 0; x < 7; ++x) vzero(acc[y][x]);
         const size_t rc = (size_t)r * C2 + c;
-        w7_dx_tile<0, 0, VT>(M, MC, rc + Cb, acc);
-        w7_dx_tile<0, 1, VT>(M, MC, rc + Cb, acc);
-        w7_dx_tile<1, 0, VT>(M, MC, rc + Cb, acc);
-        w7_dx_tile<1, 1, VT>(M, MC, rc + Cb, acc);
+        w7_for_all_tiles([&](auto t) __attribute__((always_inline)) { w7_dx_tile<t.KA, t.KB, VT>(M, MC, rc + Cb, acc); });
 #pragma unroll
         for (int y = 0; y < 7; ++y)
 #pragma unroll
@@ -613,10 +459,7 @@ __global__ __launch_bounds__(256, CIM_W7_MF_WAVES) void wino7_dx_maskfold_kernel
                 vfma(z, m, acc[y][x]);
                 acc[y][x] = z;
             }
-        w7_dx_tile<0, 0, VT>(M, MC, rc, acc);
-        w7_dx_tile<0, 1, VT>(M, MC, rc, acc);
-        w7_dx_tile<1, 0, VT>(M, MC, rc, acc);
-        w7_dx_tile<1, 1, VT>(M, MC, rc, acc);
+        w7_for_all_tiles([&](auto t) __attribute__((always_inline)) { w7_dx_tile<t.KA, t.KB, VT>(M, MC, rc, acc); });
 #pragma unroll
         for (int y = 0; y < 7; ++y)
 #pragma unroll
@@ -650,45 +493,34 @@ __device__ __forceinline__ void w7_wgrad_tile(const float* __restrict__ dU, size
                 if (W7_AW[KB][b][j] != 0.0f) vfma(acc[a][b], W7_AW[KB][b][j], s[a][j]);
 }
 
-// one lane = VW consecutive output channels of one input channel (VW = 4 needs Cout % 4 == 0, else the launcher takes VW = 1)
-template <int VW>
+// one lane = one (ci, co); the fallback for shapes the rows kernel below does not take
 __global__ __launch_bounds__(256) void wino7_wgrad_out_kernel(const float* __restrict__ dU, float* __restrict__ dW, int Cout,
                                                               int Cin) {
-    typedef typename w7_vec<VW>::T VT;
-    const size_t idx = ((size_t)blockIdx.x * 256 + threadIdx.x) * VW;     // (ci, co), co fastest
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;     // (ci, co), co fastest
     const size_t KN = (size_t)Cin * Cout;
     if (idx >= KN) return;
     const int ci = (int)(idx / Cout), co = (int)(idx % Cout);
-    VT acc[3][3];
+    float acc[3][3];
 #pragma unroll
     for (int a = 0; a < 3; ++a)
 #pragma unroll
-        for (int b = 0; b < 3; ++b) vzero(acc[a][b]);
-    w7_wgrad_tile<0, 0, VT>(dU, KN, idx, acc);
-    w7_wgrad_tile<0, 1, VT>(dU, KN, idx, acc);
-    w7_wgrad_tile<1, 0, VT>(dU, KN, idx, acc);
-    w7_wgrad_tile<1, 1, VT>(dU, KN, idx, acc);
+        for (int b = 0; b < 3; ++b) acc[a][b] = 0.0f;
+    w7_for_all_tiles([&](auto t) __attribute__((always_inline)) { w7_wgrad_tile<t.KA, t.KB, float>(dU, KN, idx, acc); });
+    float* dst = dW + ((size_t)co * Cin + ci) * 9;
 #pragma unroll
-    for (int l = 0; l < VW; ++l) {
-        float* dst = dW + ((size_t)(co + l) * Cin + ci) * 9;
+    for (int a = 0; a < 3; ++a)
 #pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 3; ++b) dst[a * 3 + b] = vget(acc[a][b], l);
-    }
+        for (int b = 0; b < 3; ++b) dst[a * 3 + b] = acc[a][b];
 }
 
 // The same transform with COALESCED stores: the lanes of a wave run along co (dU's contiguous index), but dW [Cout][Cin][3][3] keeps
 // co OUTERMOST - a lane's nine results are 36 bytes, the next lane's 73 KB away: 576 scattered 4-byte stores per wave cost half of
-// the kernel (0.213 ms; 0.104 with the stores removed).  Workgroup = 64 co x CIM_W7_WG_CI ci (wave w takes ci0 + w): the results of a
-// co row pass through LDS and leave as one run of 9 CIM_W7_WG_CI floats per row.  Bit-identical results.
-// grid = (Cout / 64, Cin / CIM_W7_WG_CI); block = 64 CIM_W7_WG_CI.
-#ifndef CIM_W7_WG_CI
-#define CIM_W7_WG_CI 4
-#endif
-__global__ __launch_bounds__(64 * CIM_W7_WG_CI) void wino7_wgrad_out_rows_kernel(const float* __restrict__ dU, float* __restrict__ dW,
+// the kernel (0.213 ms; 0.104 with the stores removed).  Workgroup = 64 co x W7_WG_CI ci (wave w takes ci0 + w): the results of a
+// co row pass through LDS and leave as one run of 9 W7_WG_CI floats per row.  Bit-identical results.
+// grid = (Cout / 64, Cin / W7_WG_CI); block = 64 W7_WG_CI.
+__global__ __launch_bounds__(64 * W7_WG_CI) void wino7_wgrad_out_rows_kernel(const float* __restrict__ dU, float* __restrict__ dW,
                                                                                  int Cout, int Cin) {
-    constexpr int NCI = CIM_W7_WG_CI, ROW = 9 * NCI;
+    constexpr int NCI = W7_WG_CI, ROW = 9 * NCI;
     __shared__ float t[64][ROW + 1];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int co0 = blockIdx.x * 64, ci0 = blockIdx.y * NCI;
@@ -699,10 +531,7 @@ __global__ __launch_bounds__(64 * CIM_W7_WG_CI) void wino7_wgrad_out_rows_kernel
     for (int a = 0; a < 3; ++a)
 #pragma unroll
         for (int b = 0; b < 3; ++b) acc[a][b] = 0.0f;
-    w7_wgrad_tile<0, 0, float>(dU, KN, idx, acc);
-    w7_wgrad_tile<0, 1, float>(dU, KN, idx, acc);
-    w7_wgrad_tile<1, 0, float>(dU, KN, idx, acc);
-    w7_wgrad_tile<1, 1, float>(dU, KN, idx, acc);
+    w7_for_all_tiles([&](auto t) __attribute__((always_inline)) { w7_wgrad_tile<t.KA, t.KB, float>(dU, KN, idx, acc); });
 #pragma unroll
     for (int a = 0; a < 3; ++a)
 #pragma unroll
@@ -718,48 +547,35 @@ __global__ __launch_bounds__(64 * CIM_W7_WG_CI) void wino7_wgrad_out_rows_kernel
 // (c, h, w) flatten of the conv output and its adjoint, fused with the ReLU mask.
 // The reference flattens MaskFuse's NCHW conv output with .view(N, -1) (resnet50.py:135): seg_fc.0's weight columns
 // are in (c, h, w) order.  The kernels here keep activations channels-last, so the flatten is a per-ROI [PP][C] ->
-// [C][PP] transpose (forward) and, in the backward, the transpose back fused with the conv's ReLU mask
-// (dy = dflat^T * (y > 0)): one pass each instead of a strided copy + compare + multiply.
+// [C][PP] transpose (forward: flatten_chw_pair_kernel below, straight into a pair image) and, in the backward, the transpose
+// back fused with the conv's ReLU mask (dy = dflat^T * (y > 0)): one pass instead of a strided copy + compare + multiply.
 // Workgroup = (ROI, 64-channel chunk), staged through a [PP][65] LDS tile: both global sides are contiguous runs
 // (256 B along C, 64 * PP floats along (c, p)).
-// bsum (backward, optional): [R][C] per-ROI sums over the PP pixels of the masked gradient - the conv's bias gradient is
+// bsum (optional): [R][C] per-ROI sums over the PP pixels of the masked gradient - the conv's bias gradient is
 // their sum over R (one small deterministic reduce instead of a pass over the 200 MB gradient).
-template <bool FWD>
-__global__ __launch_bounds__(256) void flatten_chw_kernel(const float* __restrict__ src, const float* __restrict__ y,
-                                                          float* __restrict__ dst, int PP, int C, float* __restrict__ bsum) {
+__global__ __launch_bounds__(256) void flatten_chw_bwd_kernel(const float* __restrict__ src, const float* __restrict__ y,
+                                                              float* __restrict__ dst, int PP, int C, float* __restrict__ bsum) {
     __shared__ float t[64][65];
     const int r = blockIdx.x, c0 = blockIdx.y * 64, tid = threadIdx.x;
     const size_t base = (size_t)r * PP * C;
-    if (FWD) {
-        for (int e = tid; e < PP * 64; e += 256) {
-            const int p = e >> 6, c = e & 63;
-            t[p][c] = src[base + (size_t)p * C + c0 + c];
-        }
+    for (int e = tid; e < PP * 64; e += 256) {
+        const int c = e / PP, p = e - c * PP;
+        t[p][c] = src[base + (size_t)c0 * PP + e];
+    }
+    __syncthreads();
+    float part = 0.0f;
+    for (int e = tid; e < PP * 64; e += 256) {
+        const int p = e >> 6, c = e & 63;
+        const size_t o = base + (size_t)p * C + c0 + c;
+        const float v = (y == nullptr || y[o] > 0.0f) ? t[p][c] : 0.0f;
+        dst[o] = v;
+        part += v;                       // this thread's channel is tid & 63 in every iteration
+    }
+    if (bsum != nullptr) {
         __syncthreads();
-        for (int e = tid; e < PP * 64; e += 256) {
-            const int c = e / PP, p = e - c * PP;
-            dst[base + (size_t)c0 * PP + e] = t[p][c];
-        }
-    } else {
-        for (int e = tid; e < PP * 64; e += 256) {
-            const int c = e / PP, p = e - c * PP;
-            t[p][c] = src[base + (size_t)c0 * PP + e];
-        }
+        t[tid >> 6][tid & 63] = part;
         __syncthreads();
-        float part = 0.0f;
-        for (int e = tid; e < PP * 64; e += 256) {
-            const int p = e >> 6, c = e & 63;
-            const size_t o = base + (size_t)p * C + c0 + c;
-            const float v = (y == nullptr || y[o] > 0.0f) ? t[p][c] : 0.0f;
-            dst[o] = v;
-            part += v;                       // this thread's channel is tid & 63 in every iteration
-        }
-        if (bsum != nullptr) {
-            __syncthreads();
-            t[tid >> 6][tid & 63] = part;
-            __syncthreads();
-            if (tid < 64) bsum[(size_t)r * C + c0 + tid] = (t[0][tid] + t[1][tid]) + (t[2][tid] + t[3][tid]);
-        }
+        if (tid < 64) bsum[(size_t)r * C + c0 + tid] = (t[0][tid] + t[1][tid]) + (t[2][tid] + t[3][tid]);
     }
 }
 
@@ -801,29 +617,22 @@ __global__ __launch_bounds__(256) void flatten_chw_pair_kernel(const float* __re
 
 }  // namespace
 
-#define WINO_GEOM_OK() CIM_CHECK_ARG(R > 0 && P > 0 && P <= 64 && C > 0 && C % 4 == 0)
-
 extern "C" int cim_wino_wgrad_output(const float* dU, float* dW, int Cout, int Cin, int tile, void* stream) {
     CIM_CHECK_ARG(dU && dW && Cout > 0 && Cin > 0);
     CIM_CHECK_ARG(tile == 7);         // (the F(2x2,3x3) / F(4x4,3x3) stages are test infrastructure: experiments/csrc/winograd_all.hip)
     const size_t n = (size_t)Cout * Cin;
-    if (Cout % 64 == 0 && Cin % CIM_W7_WG_CI == 0 && Cin / CIM_W7_WG_CI <= 65535) {
-        hipLaunchKernelGGL(wino7_wgrad_out_rows_kernel, dim3(Cout / 64, Cin / CIM_W7_WG_CI), dim3(64 * CIM_W7_WG_CI), 0, cim::as_stream(stream),
-                           dU, dW, Cout, Cin);
-        CIM_CHECK_LAUNCH();
-        return 0;
-    }
-    if (CIM_W7_VWG == 4 && Cout % 4 == 0)
-        hipLaunchKernelGGL(wino7_wgrad_out_kernel<4>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, cim::as_stream(stream), dU, dW, Cout, Cin);
-    else hipLaunchKernelGGL(wino7_wgrad_out_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, cim::as_stream(stream), dU, dW, Cout, Cin);
+    if (Cout % 64 == 0 && Cin % W7_WG_CI == 0 && Cin / W7_WG_CI <= 65535)
+        hipLaunchKernelGGL(wino7_wgrad_out_rows_kernel, dim3(Cout / 64, Cin / W7_WG_CI), dim3(64 * W7_WG_CI), 0, cim::as_stream(stream), dU,
+                           dW, Cout, Cin);
+    else hipLaunchKernelGGL(wino7_wgrad_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, cim::as_stream(stream), dU, dW, Cout, Cin);
     CIM_CHECK_LAUNCH();
     return 0;
 }
 
 extern "C" int cim_wino_dx_adjoint_output(const float* M, float* dx, int R, int P, int C, int tile, void* stream) {
-    WINO_GEOM_OK();
+    CIM_CHECK_ARG(R > 0 && P > 0 && P <= 64 && C > 0 && C % 4 == 0);
     CIM_CHECK_ARG(M && dx && tile == 7 && P == 7 && R <= 2147483647);
-    int chunks = (C + 256 * CIM_W7_VDX - 1) / (256 * CIM_W7_VDX);
+    int chunks = (C + 256 * W7_VDX - 1) / (256 * W7_VDX);
     if (chunks > 4) chunks = 4;
     hipLaunchKernelGGL(wino7_dx_kernel, dim3(R, chunks), dim3(256), 0, cim::as_stream(stream), M, dx, R, C);
     CIM_CHECK_LAUNCH();
@@ -832,7 +641,7 @@ extern "C" int cim_wino_dx_adjoint_output(const float* M, float* dx, int R, int 
 
 extern "C" int cim_wino7_dx_maskfold(const float* M, const float* masks, float* dbox, int R, int Cb, void* stream) {
     CIM_CHECK_ARG(M && masks && dbox && R > 0 && Cb > 0 && Cb % 4 == 0);
-    int chunks = (Cb + 256 * CIM_W7_VMF - 1) / (256 * CIM_W7_VMF);
+    int chunks = (Cb + 256 * W7_VMF - 1) / (256 * W7_VMF);
     if (chunks > 4) chunks = 4;
     hipLaunchKernelGGL(wino7_dx_maskfold_kernel, dim3(R, chunks), dim3(256), 0, cim::as_stream(stream), M, masks, dbox, R, Cb);
     CIM_CHECK_LAUNCH();
@@ -898,7 +707,7 @@ extern "C" int cim_flatten_chw_pair(const float* src, void* dst, const float* sc
 extern "C" int cim_flatten_chw_bwd_bias(const float* src, const float* relu_y, float* dst, float* bias_partial, int R, int PP,
                                         int C, void* stream) {
     CIM_CHECK_ARG(src && dst && R > 0 && PP > 0 && PP <= 64 && C > 0 && C % 64 == 0 && C / 64 <= 65535);
-    hipLaunchKernelGGL(flatten_chw_kernel<false>, dim3(R, C / 64), dim3(256), 0, cim::as_stream(stream), src, relu_y, dst, PP, C, bias_partial);
+    hipLaunchKernelGGL(flatten_chw_bwd_kernel, dim3(R, C / 64), dim3(256), 0, cim::as_stream(stream), src, relu_y, dst, PP, C, bias_partial);
     CIM_CHECK_LAUNCH();
     return 0;
 }

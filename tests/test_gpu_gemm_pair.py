@@ -381,6 +381,55 @@ def test_output_amax_and_flatten_pair(dev):
     _close_to(d[:R], flat.cpu().numpy(), float(y0.max()) * 2.0 ** -38)
 
 
+@pytest.mark.parametrize("Cout,Cin", [(128, 72), (40, 24)])          # the rows kernel (Cout % 64 == 0); the one-lane-per-element fallback
+def test_wgrad_output_matches_the_fp32_stage(dev, Cout, Cin):
+    from cim_amd import _lib
+    from experiments import _lib as _xlib           # the fp32 stages of the same tiling: the comparator (test infrastructure)
+    st = _lib.stream_ptr()
+    g = torch.Generator().manual_seed(13 + Cout)
+    dU = torch.randn(121, Cin, Cout, generator=g).to(dev)
+    w0 = torch.full((Cout, Cin, 3, 3), float("nan"), device=dev)
+    w1 = torch.full((Cout, Cin, 3, 3), float("nan"), device=dev)
+    _xlib.call("cim_wino_wgrad_output", dU.data_ptr(), w0.data_ptr(), Cout, Cin, 7, st)
+    _lib.call("cim_wino_wgrad_output", dU.data_ptr(), w1.data_ptr(), Cout, Cin, 7, st)
+    assert torch.equal(w0, w1)                      # (the rows kernel only reorders the stores)
+
+
+@pytest.mark.parametrize("C", [192, 2564])          # below one 512-channel chunk; more than the four chunks of the grid
+def test_dx_adjoint_output_matches_the_fp32_stage(dev, C):
+    from cim_amd import _lib
+    from experiments import _lib as _xlib           # the fp32 stages of the same tiling: the comparator (test infrastructure)
+    st = _lib.stream_ptr()
+    g = torch.Generator().manual_seed(14 + C)
+    R = 5
+    M = torch.randn(121, R, C, generator=g).to(dev)
+    d0 = torch.full((R, 7, 7, C), float("nan"), device=dev)
+    d1 = torch.full((R, 7, 7, C), float("nan"), device=dev)
+    _xlib.call("cim_wino_dx_adjoint_output", M.data_ptr(), d0.data_ptr(), R, 7, C, 7, st)
+    _lib.call("cim_wino_dx_adjoint_output", M.data_ptr(), d1.data_ptr(), R, 7, C, 7, st)
+    assert torch.equal(d0, d1)
+
+
+@pytest.mark.parametrize("Cb", [256, 1280])         # one 256-channel chunk; more than the four chunks of the grid
+def test_dx_maskfold_is_the_adjoint_output_folded_with_the_mask(dev, Cb):
+    """cim_wino7_dx_maskfold writes dbox = dcat[..., :Cb] + mask * dcat[..., Cb:] of the dcat that cim_wino_dx_adjoint_output
+    writes for the 2 Cb channels (lib/modeling/resnet50.py:131-134 differentiated).  It scales the masked half's 49 sums and
+    accumulates the plain half on top - another summation order than fma(mask, hi, lo) afterwards: the bound is the one
+    test_roi_align_wino7_pair_image_is_bit_identical_to_the_two_kernel_path applies to this reordering."""
+    from cim_amd import _lib
+    st = _lib.stream_ptr()
+    g = torch.Generator().manual_seed(15 + Cb)
+    R = 6
+    M = torch.randn(121, R, 2 * Cb, generator=g).to(dev)
+    masks = (torch.rand(R, 7, 7, generator=g) > 0.4).float().to(dev)
+    dcat = torch.full((R, 7, 7, 2 * Cb), float("nan"), device=dev)
+    _lib.call("cim_wino_dx_adjoint_output", M.data_ptr(), dcat.data_ptr(), R, 7, 2 * Cb, 7, st)
+    ref = dcat[..., :Cb] + masks[..., None] * dcat[..., Cb:]
+    got = torch.full((R, 7, 7, Cb), float("nan"), device=dev)
+    _lib.call("cim_wino7_dx_maskfold", M.data_ptr(), masks.data_ptr(), got.data_ptr(), R, Cb, st)
+    assert float((got - ref).abs().max()) <= 2e-6 * float(ref.abs().max())
+
+
 @pytest.mark.parametrize("r", [37, 64])
 def test_maskfuse_pair_function_vs_per_layer_path(dev, r):
     """The fused head Function on pair images against the per-layer f16x2 Functions (same module parameters) and against

@@ -1,5 +1,6 @@
 """cim_wino7_flatten_bwd_dy_pair alone (dX [R][C*49] + saved conv output -> E', D' pair images) beside the three launches it replaces;
-every cim_amd/libcim_hip_alt_fb*.so is timed next to the product library.    python tools/bench_dy_fused.py [R] [C]"""
+every cim_amd/libcim_hip_alt_fb*.so (any other build of the library, e.g. another commit's: `python -m cim_amd.build
+--out=.../libcim_hip_alt_fb_NAME.so` in its checkout) is timed next to the product library.    python tools/bench_dy_fused.py [R] [C]"""
 import ctypes, glob, os, sys
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))

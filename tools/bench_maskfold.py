@@ -1,4 +1,5 @@
-"""cim_wino7_dx_maskfold alone (Md [121][R][2Cb] -> dbox [R][7][7][Cb]); every cim_amd/libcim_hip_alt_mf*.so beside the product library.
+"""cim_wino7_dx_maskfold alone (Md [121][R][2Cb] -> dbox [R][7][7][Cb]); every cim_amd/libcim_hip_alt_mf*.so beside the product library
+(any other build of the library, e.g. another commit's: `python -m cim_amd.build --out=.../libcim_hip_alt_mf_NAME.so` in its checkout).
     python tools/bench_maskfold.py [R] [Cb]"""
 import ctypes, glob, os, sys
 import torch

@@ -1,4 +1,5 @@
-"""cim_wino_wgrad_output alone (dU [121][Cin][Cout] -> dW [Cout][Cin][3][3]); every cim_amd/libcim_hip_alt_wg*.so beside the product."""
+"""cim_wino_wgrad_output alone (dU [121][Cin][Cout] -> dW [Cout][Cin][3][3]); every cim_amd/libcim_hip_alt_wg*.so beside the product
+(any other build of the library, e.g. another commit's: `python -m cim_amd.build --out=.../libcim_hip_alt_wg_NAME.so` in its checkout)."""
 import ctypes, glob, os, sys
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
