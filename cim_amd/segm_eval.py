@@ -5,7 +5,8 @@ Replaces pycocotools' mask.encode / decode and COCOeval.evaluate / accumulate / 
 inference (tools/evaluation.py:72-145, 236-241; lib/datasets/json_inference.py:24-55).  Masks are DEVICE tensors; a CPU
 tensor is an error (no CPU fallback).  `SegmEvaluator.add_image` only launches work on the current stream, so the masks of
 an image may be freed or reused as soon as it returns; `accumulate` returns device tensors, `to_host` copies them.
-The reference-shaped wrappers are cim_amd.utils.mask_eval_utils.coco_encode and cim_amd.datasets.json_inference.
+`poly_masks` fills COCO polygon segmentations into the same packed masks (csrc/poly_fill.hip), so polygon ground truth
+needs no pycocotools either.  The reference-shaped wrappers are cim_amd.utils.mask_eval_utils.coco_encode and cim_amd.datasets.json_inference.
 """
 import numpy as np
 import torch
@@ -17,6 +18,8 @@ MAX_HW = 1 << 22                # CIM_SEGM_MAX_HW of include/cim_hip.h
 MAX_GT = 1024                   # CIM_SEGM_MAX_GT: ground truths per image
 MAX_DT = 8192                   # CIM_DETECT_MAX_N: detections per (image, category), and maxDets[-1]
 MAX_T, MAX_R, MAX_A, MAX_M = 16, 128, 8, 4
+MAX_POLY_POINTS = 1 << 26       # CIM_POLY_MAX_POINTS: dense points of the polygons of one poly_masks call
+MAX_POLY_COORD = float(1 << 20)
 
 AREA_LABELS = ("all", "small", "medium", "large")
 
@@ -150,6 +153,71 @@ def rle_decode(rles, device=None, size=None):
     return packed, (h, w)
 
 
+def _polygon_arrays(polygons_per_annotation, h, w):
+    """The polygons of all annotations as the arrays of cim_poly_fill (include/cim_hip.h), after its refusals: (xy f64,
+    poly_off, poly_ann, edge_off int32, dense points in all).  O(vertices) host work: the device needs the total before it
+    can be launched, and a refusal needs no device round trip."""
+    words_of(h, w)                                                       # (refuses h w > CIM_SEGM_MAX_HW)
+    flat, sizes, ann = [], [], []
+    for i, polys in enumerate(polygons_per_annotation):
+        for xy in polys:
+            a = np.asarray(xy, dtype=np.float64).ravel()
+            if a.size % 2:
+                raise ValueError("cim_amd.segm_eval: annotation %d: a polygon of odd length %d" % (i, a.size))
+            if a.size < 6:
+                raise ValueError("cim_amd.segm_eval: annotation %d: a polygon of %d numbers (need >= 6; pycocotools reads 4 "
+                                 "numbers as a box, this does not)" % (i, a.size))
+            if not np.isfinite(a).all():
+                raise ValueError("cim_amd.segm_eval: annotation %d: a non-finite polygon coordinate" % i)
+            if np.abs(a).max() > MAX_POLY_COORD:
+                raise ValueError("cim_amd.segm_eval: annotation %d: a polygon coordinate outside [-2^20, 2^20]" % i)
+            flat.append(a)
+            sizes.append(a.size // 2)
+            ann.append(i)
+    xy = np.concatenate(flat) if flat else np.zeros(0, np.float64)
+    poly_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    r = (5.0 * xy + .5).astype(np.int64)                                 # (int)(5 x + .5), as the device rounds them
+    X, Y = r[0::2], r[1::2]
+    nxt = np.arange(1, X.size + 1)
+    nxt[poly_off[1:] - 1] = poly_off[:-1]                                # a polygon's last edge returns to its first vertex
+    steps = np.maximum(np.abs(X[nxt] - X), np.abs(Y[nxt] - Y)) + 1
+    edge_off = np.concatenate([[0], np.cumsum(steps)]).astype(np.int64)
+    total = int(edge_off[-1])
+    if total > MAX_POLY_POINTS:
+        raise ValueError("cim_amd.segm_eval: %d dense points in one call, the kernels take <= %d (CIM_POLY_MAX_POINTS)"
+                         % (total, MAX_POLY_POINTS))
+    return xy, poly_off.astype(np.int32), np.asarray(ann, np.int32), edge_off.astype(np.int32), total
+
+
+def poly_masks(polygons_per_annotation, h, w, device=None):
+    """COCO polygon segmentations -> device int64 [n, words] packed masks: pycocotools' frPyObjects + merge (annToRLE's
+    polygon case) per annotation.  polygons_per_annotation[i] is annotation i's `segmentation` list: polygons [x0, y0, x1,
+    y1, ...] in pixel coordinates, filled by COCO's rule and OR-ed (csrc/poly_fill.hip).  ValueError for a
+    polygon of odd length or fewer than 6 numbers, a non-finite coordinate or one outside [-2^20, 2^20], h w > 2^22, or
+    more than CIM_POLY_MAX_POINTS dense points in the call.  Launches on the current stream; does not synchronise."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise _lib.CimHipError("cim_amd.segm_eval: poly_masks needs a CUDA/HIP device (no CPU fallback)")
+    h, w = int(h), int(w)
+    polys = list(polygons_per_annotation)
+    xy, poly_off, poly_ann, edge_off, total = _polygon_arrays(polys, h, w)
+    n, n_poly = len(polys), poly_ann.size
+    packed = torch.empty((n, words_of(h, w)), dtype=torch.int64, device=dev)
+    if n == 0:
+        return packed
+    ws_bytes = _lib.call("cim_poly_ws_bytes", n_poly, h, w)
+    if ws_bytes < 0:
+        raise ValueError(_err())
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    if n_poly:
+        xy_d, po_d, pa_d, eo_d = (_upload(a, dev) for a in (xy, poly_off, poly_ann, edge_off))
+    else:
+        xy_d = po_d = pa_d = eo_d = None
+    _lib.call("cim_poly_fill", _lib.ptr(xy_d), _lib.ptr(po_d), _lib.ptr(pa_d), _lib.ptr(eo_d), n_poly, xy.size // 2, total, n, h, w,
+              ws.data_ptr(), packed.data_ptr(), _lib.stream_ptr())
+    return packed
+
+
 def record_layout(nd, ng, A, T):
     """Byte offsets of one (image, category) record (csrc/segm_eval.hip: rec_layout)."""
     L = {"dtm": 0}
@@ -221,7 +289,7 @@ class SegmEvaluator(object):
                               _upload(np.asarray(self.max_dets, np.int32), d))
         return self._params_d
 
-    def _masks(self, x, n, what):
+    def _masks(self, x, n, what, size=None, polygons=False):
         """-> (device packed [n, words] or None, (H, W) or None)"""
         if x is None:
             if n:
@@ -244,14 +312,35 @@ class SegmEvaluator(object):
             raise ValueError("cim_amd.segm_eval: %d %s, %d RLEs" % (n, what, len(rles)))
         if n == 0:
             return None, None
-        packed, hw = rle_decode(rles, self.device)
-        return packed, hw
+        is_poly = [isinstance(r, (list, tuple)) for r in rles]
+        if not any(is_poly):
+            packed, hw = rle_decode(rles, self.device)
+            if size is not None and hw != tuple(size):
+                raise ValueError("cim_amd.segm_eval: %s RLEs of size %s, asked for %s (H x W must match)" % (what, hw, tuple(size)))
+            return packed, hw
+        if not polygons:
+            raise ValueError("cim_amd.segm_eval: %s must be masks or RLEs (polygons are taken for ground truths only)" % what)
+        # polygon lists among the RLEs: the polygons' rows in one launch, the RLEs' rows decoded and copied over theirs
+        rest = [j for j in range(n) if not is_poly[j]]
+        sizes = {tuple(int(v) for v in rles[j]["size"]) for j in rest} | ({tuple(int(v) for v in size)} if size is not None else set())
+        if len(sizes) > 1:
+            raise ValueError("cim_amd.segm_eval: %s of different sizes %s (H x W must match)" % (what, sorted(sizes)))
+        if not sizes:
+            raise ValueError("cim_amd.segm_eval: polygon %s need the image's size=(H, W)" % what)
+        h, w = sizes.pop()
+        packed = poly_masks([r if p else [] for r, p in zip(rles, is_poly)], h, w, self.device)
+        if rest:
+            dec, _ = rle_decode([rles[j] for j in rest], self.device)
+            packed.index_copy_(0, _upload(np.asarray(rest, np.int64), self.device), dec)
+        return packed, (h, w)
 
-    def add_image(self, img_id, gt, gt_cat_ids, gt_iscrowd, gt_area, gt_ids, dt, dt_cat_ids, dt_scores):
-        """One image: ground truths (device masks [G, H, W], or COCO RLEs) with their category ids, iscrowd flags,
-        annotation `area` fields and annotation ids (host sequences); detections (device masks [D, H, W], COCO RLEs, or
-        (device proposal masks [N, H, W], kept proposal indices [D])) with category ids (host) and fp32 scores (device
-        tensor or host array).  Ground truths and detections of categories outside cat_ids are left out, as COCOeval does.
+    def add_image(self, img_id, gt, gt_cat_ids, gt_iscrowd, gt_area, gt_ids, dt, dt_cat_ids, dt_scores, size=None):
+        """One image: ground truths (device masks [G, H, W], or a list of COCO RLEs and / or polygon lists - an annotation's
+        `segmentation` as the file stores it) with their category ids, iscrowd flags, annotation `area` fields and annotation
+        ids (host sequences); detections (device masks [D, H, W], COCO RLEs, or (device proposal masks [N, H, W], kept
+        proposal indices [D])) with category ids (host) and fp32 scores (device tensor or host array).  size = (H, W) of the
+        image: what polygons are filled on (needed unless an RLE among the ground truths gives it).
+        Ground truths and detections of categories outside cat_ids are left out, as COCOeval does.
         Launches the image's packing, IoU and matching on the current stream; does not synchronise."""
         img_id = int(img_id)
         if img_id not in self._img_rank:
@@ -286,7 +375,7 @@ class SegmEvaluator(object):
             if np.isnan(sh).any():
                 raise ValueError("cim_amd.segm_eval: NaN score")
             scores_d = _upload(sh, self.device) if D else None
-        gp, ghw = self._masks(gt, G, "ground truths")
+        gp, ghw = self._masks(gt, G, "ground truths", size, True)
         dp, dhw = self._masks(dt, D, "detections")
         if ghw is not None and dhw is not None and ghw != dhw:
             raise ValueError("cim_amd.segm_eval: image %d: detection masks %s, ground-truth masks %s (H x W must match)"

@@ -318,6 +318,31 @@ int cim_segm_accumulate(const int64_t* entries, int n_entries, long long E, int 
                         const int64_t* round_off, int rounds, const double* rec_thrs, int R, const int32_t* max_dets, int M,
                         int A, int T, void* ws, double* precision, double* recall, double* scores, void* stream);
 
+/* ------------------------------------------------------------------ polygon ground truth for mask AP (ABI-16 addition)
+ * COCO's polygon fill (maskApi.c rleFrPoly, then merge as a union): what pycocotools' annToRLE / frPyObjects does to an
+ * annotation whose `segmentation` is a list of polygons, straight to the packed masks above (csrc/poly_fill.hip).
+ * Additive: cim_abi_version() stays 16.  Exactness contract (bit-identical to tests/golden/poly_np.py): DESIGN.md 4.12.
+ *
+ * cim_poly_fill, all pointers device memory:
+ *   xy [2 n_vert] f64       the polygons' coordinates x0, y0, x1, y1, ... back to back (each finite, within [-2^20, 2^20])
+ *   poly_off [n_poly + 1]   int32 first vertex of each polygon (ascending, poly_off[n_poly] = n_vert, >= 3 vertices each)
+ *   poly_ann [n_poly]       int32 annotation (row of `packed`) each polygon belongs to; a value outside 0..n_ann-1 is skipped
+ *   edge_off [n_vert + 1]   int32 exclusive prefix of the edges' dense-point counts: edge j runs from vertex j to the next
+ *                           vertex of its polygon (the last one back to the first) and has max(|dX|, |dY|) + 1 points, X =
+ *                           (int)(5 x + .5), Y likewise; edge_off[n_vert] = n_points
+ *   packed [n_ann][words]   uint64 out, words = cim_segm_words(H, W): the OR of each annotation's polygon fills, bits past
+ *                           H W zero, an annotation without polygons empty
+ * ws: cim_poly_ws_bytes(n_poly, H, W) bytes, 8-byte aligned, no initial content; one ws serves one call at a time.
+ * Two memsets and two launches on `stream` (crossings: one lane per dense point; fill: one workgroup per polygon); no host
+ * synchronisation.  Refused before any launch (-1): H W > CIM_SEGM_MAX_HW, n_points > CIM_POLY_MAX_POINTS (2^26: one lane
+ * per point keeps the crossing launch at <= 2^18 workgroups and every offset in int32), counts that cannot fit together.
+ * The coordinates are the caller's to check (cim_amd.segm_eval.poly_masks refuses odd lengths, fewer than 6 numbers,
+ * non-finite values and values outside [-2^20, 2^20]); whatever the arrays hold, nothing is read or written out of range. */
+#define CIM_POLY_MAX_POINTS (1 << 26)   /* dense points per call */
+long long cim_poly_ws_bytes(int n_poly, int H, int W);
+int cim_poly_fill(const double* xy, const int32_t* poly_off, const int32_t* poly_ann, const int32_t* edge_off, int n_poly,
+                  int n_vert, long long n_points, int n_ann, int H, int W, void* ws, uint64_t* packed, void* stream);
+
 /* ------------------------------------------------------------------ training inputs from proposal masks (ABI-16 addition)
  * Replaces tools/pre/generate_7_7_{voc,coco}.py:35-42 (tight boxes, PIL nearest resize to S x S) and the label assignment of
  * tools/pre/AGPL_label_assign.py:154-180 / point_level_label_assign.py:66-93 (lib/utils/mask_utils.py:6-18).
