@@ -22,6 +22,8 @@ ALIASES = {
     "modeling.HRNet": "cim_amd.modeling.HRNet",                        # lib/modeling/HRNet.py
     "nn.parallel": "cim_amd.nn.parallel",                              # lib/nn/parallel/__init__.py (DataParallel)
     "nn.parallel.data_parallel": "cim_amd.nn.parallel.data_parallel",  # lib/nn/parallel/data_parallel.py
+    "datasets.voc_eval": "cim_amd.datasets.voc_eval",                  # lib/datasets/voc_eval.py
+    "datasets.dis_eval": "cim_amd.datasets.dis_eval",                  # lib/datasets/dis_eval.py
 }
 
 

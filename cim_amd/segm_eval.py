@@ -219,7 +219,7 @@ def poly_masks(polygons_per_annotation, h, w, device=None):
 
 
 def record_layout(nd, ng, A, T):
-    """Byte offsets of one (image, category) record (csrc/segm_eval.hip: rec_layout)."""
+    """Byte offsets of one (image, category) record (csrc/eval_match.h: rec_layout)."""
     L = {"dtm": 0}
     L["score"] = L["dtm"] + 8 * A * T * nd
     L["order"] = L["score"] + 4 * nd
@@ -342,6 +342,38 @@ class SegmEvaluator(object):
         image: what polygons are filled on (needed unless an RLE among the ground truths gives it).
         Ground truths and detections of categories outside cat_ids are left out, as COCOeval does.
         Launches the image's packing, IoU and matching on the current stream; does not synchronise."""
+        img_id, gcat, crowd, garea, gids, dcat, scores_d = self._image_fields(img_id, gt_cat_ids, gt_iscrowd, gt_area, gt_ids,
+                                                                              dt_cat_ids, dt_scores)
+        G, D = gcat.size, dcat.size
+        gp, ghw = self._masks(gt, G, "ground truths", size, True)
+        dp, dhw = self._masks(dt, D, "detections")
+        if ghw is not None and dhw is not None and ghw != dhw:
+            raise ValueError("cim_amd.segm_eval: image %d: detection masks %s, ground-truth masks %s (H x W must match)"
+                             % (img_id, dhw, ghw))
+        hw = ghw or dhw
+        info, meta, ndl, ngl, rec_off, pair_off = self._image_groups(img_id, dcat, gcat, crowd, gids)
+        if meta is None:
+            return
+        dev = self.device
+        T, A = len(self.iou_thrs), len(self.area_rng)
+        ws_bytes = _lib.call("cim_segm_image_ws_bytes", D, G, pair_off)
+        if ws_bytes < 0:
+            raise ValueError(_err())
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        records = torch.empty(max(rec_off, 8), dtype=torch.uint8, device=dev)
+        words = words_of(*hw)
+        meta_d = _upload(meta, dev)
+        garea_d = _upload(garea, dev) if G else None
+        gids_d = _upload(gids, dev) if G else None
+        thr_d, rng_d, _, _ = self._params()
+        _lib.call("cim_segm_eval_image", _lib.ptr(dp), D, _lib.ptr(gp), G, words, _lib.ptr(scores_d), meta_d.data_ptr(),
+                  len(info["groups"]), ndl, ngl, pair_off, _lib.ptr(garea_d), _lib.ptr(gids_d), thr_d.data_ptr(), T,
+                  rng_d.data_ptr(), A, ws.data_ptr(), records.data_ptr(), _lib.stream_ptr())
+        info["records"] = records
+
+    def _image_fields(self, img_id, gt_cat_ids, gt_iscrowd, gt_area, gt_ids, dt_cat_ids, dt_scores):
+        """add_image's checks of the per-annotation and per-detection fields -> (image id, ground-truth category ids, crowd
+        flags int32, areas f64, ids int64, detection category ids, device fp32 scores or None)."""
         img_id = int(img_id)
         if img_id not in self._img_rank:
             raise ValueError("cim_amd.segm_eval: image %d is not among the evaluated image ids (COCO.loadRes asserts this)" % img_id)
@@ -375,12 +407,11 @@ class SegmEvaluator(object):
             if np.isnan(sh).any():
                 raise ValueError("cim_amd.segm_eval: NaN score")
             scores_d = _upload(sh, self.device) if D else None
-        gp, ghw = self._masks(gt, G, "ground truths", size, True)
-        dp, dhw = self._masks(dt, D, "detections")
-        if ghw is not None and dhw is not None and ghw != dhw:
-            raise ValueError("cim_amd.segm_eval: image %d: detection masks %s, ground-truth masks %s (H x W must match)"
-                             % (img_id, dhw, ghw))
-        hw = ghw or dhw
+        return img_id, gcat, crowd, garea, gids, dcat, scores_d
+
+    def _image_groups(self, img_id, dcat, gcat, crowd, gids):
+        """The image's (image, category) groups: registers the image and returns (its info, the int32 meta array of
+        cim_segm_eval_image or None when the image has no group, n_dl, n_gl, record bytes, IoU pairs)."""
         T, A = len(self.iou_thrs), len(self.area_rng)
         kd = np.array([self._cat_index.get(int(c), -1) for c in dcat], np.int64)
         kg = np.array([self._cat_index.get(int(c), -1) for c in gcat], np.int64)
@@ -410,23 +441,9 @@ class SegmEvaluator(object):
         info = {"groups": groups, "gt_ids": gids, "records": None}
         self._images[img_id] = info
         if not groups:
-            return
-        dev = self.device
+            return info, None, 0, 0, 0, 0
         meta = np.concatenate([np.asarray(meta_g, np.int32).ravel()] + [a.astype(np.int32) for a in dls + gls] + [crowd])
-        ws_bytes = _lib.call("cim_segm_image_ws_bytes", D, G, pair_off)
-        if ws_bytes < 0:
-            raise ValueError(_err())
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        records = torch.empty(max(rec_off, 8), dtype=torch.uint8, device=dev)
-        words = words_of(*hw)
-        meta_d = _upload(meta, dev)
-        garea_d = _upload(garea, dev) if G else None
-        gids_d = _upload(gids, dev) if G else None
-        thr_d, rng_d, _, _ = self._params()
-        _lib.call("cim_segm_eval_image", _lib.ptr(dp), D, _lib.ptr(gp), G, words, _lib.ptr(scores_d), meta_d.data_ptr(),
-                  len(groups), ndl, ngl, pair_off, _lib.ptr(garea_d), _lib.ptr(gids_d), thr_d.data_ptr(), T, rng_d.data_ptr(), A,
-                  ws.data_ptr(), records.data_ptr(), _lib.stream_ptr())
-        info["records"] = records
+        return info, meta, ndl, ngl, rec_off, pair_off
 
     def accumulate(self):
         """COCOeval.accumulate: {'precision' [T,R,K,A,M], 'recall' [T,K,A,M], 'scores' [T,R,K,A,M]} fp64 device tensors."""

@@ -284,7 +284,7 @@ int cim_detect_corloc(const float* scores, int ld, int N, int C, int32_t* out, v
  * input order), crowd [G].  gt_area [G] f64 is the annotations' `area`, gt_id [G] int64 their ids, iou_thrs [T] and
  * area_rng [A][2] f64 the host's values.  ws: cim_segm_image_ws_bytes(D, G, pairs) bytes.  A record holds, in rank order:
  * dtm int64 [A][T][nd] (matched ground-truth id, 0 = none), score f32 [nd], order int32 [nd], npig int32 [A], gt_order
- * int32 [A][n_gt], dt_ignore uint8 [A][T][nd], gt_ignore uint8 [A][n_gt] (layout: csrc/segm_eval.hip rec_layout).
+ * int32 [A][n_gt], dt_ignore uint8 [A][T][nd], gt_ignore uint8 [A][n_gt] (layout: csrc/eval_match.h rec_layout).
  * Accumulate (cim_segm_accumulate): entries [n_entries][6] int64 = (record device address, nd, n_gt, first element,
  * category index, 0), category-major and image-minor (ascending image id), one per (image, category) with a ground truth
  * or a detection; cat_off [K + 1] the first element of each category (E elements in all); jobs [.][3] int64 = (start,
@@ -342,6 +342,57 @@ int cim_segm_accumulate(const int64_t* entries, int n_entries, long long E, int 
 long long cim_poly_ws_bytes(int n_poly, int H, int W);
 int cim_poly_fill(const double* xy, const int32_t* poly_off, const int32_t* poly_ann, const int32_t* edge_off, int n_poly,
                   int n_vert, long long n_points, int n_ann, int H, int W, void* ws, uint64_t* packed, void* stream);
+
+/* ------------------------------------------------------------------ box evaluation (ABI-16 addition)
+ * Scores the boxes inference produced, as the reference's task_evaluation.evaluate_all does: COCOeval(..., 'bbox')
+ * (lib/datasets/json_dataset_evaluator.py:105-118), the VOC devkit's AP (lib/datasets/voc_eval.py:146-228) and CorLoc
+ * (lib/datasets/dis_eval.py:88-141); csrc/box_eval.hip.  Additive: cim_abi_version() stays 16.  Exactness contract, limits
+ * and the tie rule: DESIGN.md 4.14.  All box arithmetic is fp64, every operation rounded on its own (no contraction).
+ *
+ * cim_box_eval_image: cim_segm_eval_image with boxes in place of packed masks - the same meta, records, gt_area, gt_id,
+ * iou_thrs and area_rng, the same record layout (cim_segm_record_bytes), so cim_segm_accumulate consumes the records
+ * unchanged.  dt_box [D][4], gt_box [G][4] f64 = (x, y, w, h).  IoU: maskApi.c's bbIou operation for operation - da =
+ * D[2] D[3], ga = G[2] G[3], w = fmin(D[2] + D[0], G[2] + G[0]) - fmax(D[0], G[0]), h likewise on y, 0 when w <= 0 or
+ * h <= 0, else i = w h and i / (crowd ? da : da + ga - i).  A detection's area for the area-range rule is da (what
+ * COCO.loadRes stores for a bbox result), not a pixel count.  ws: cim_box_image_ws_bytes(D, G, pairs) bytes, 8-byte aligned.
+ * Four launches (areas, sort, IoU, match - the matcher is cim_segm_eval_image's own, csrc/eval_match.h).
+ *
+ * cim_voc_match: the whole dataset in one launch, one workgroup per (class, image) group.  groups [n_groups][4] int32 =
+ * (det_start, n_det, gt_start, n_gt) into dt_box [D][4] / dt_conf [D] f64 and gt_box [G][4] f64 / gt_difficult [G] uint8,
+ * boxes as (x1, y1, x2, y2); n_det <= CIM_DETECT_MAX_N and n_gt <= CIM_SEGM_MAX_GT per group (more are not visited; a group
+ * that does not lie inside the arrays is left alone).  Within a group detections are visited by descending confidence,
+ * equal confidences in ascending input position (a stated deviation: the reference's np.argsort(-confidence) leaves ties
+ * undefined).  Per detection voc_eval's arithmetic (the + 1 widths, inters / uni), ovmax = the maximum overlap, jmax = its
+ * first index; with ovmax > ovthresh a difficult ground truth gives neither tp nor fp, an unclaimed one tp (and is claimed),
+ * a claimed one fp; otherwise, and with n_gt = 0, fp.  mode 1 is dis_eval's rule: tp if and only if ovmax > ovthresh (no
+ * claims, no difficult flags), fp = 1 - tp.  Outputs by input position: tp, fp [D] uint8, ovmax [D] f64 (-inf without
+ * ground truth), jmax [D] int32 (-1 without ground truth).
+ *
+ * cim_voc_ap: per class, voc_eval.py:219-226 and its voc_ap.  Detections class-major, class k at class_off[k] ..
+ * class_off[k + 1] (int64 [K + 1]); npos [K] f64.  The stable sort by descending confidence over the input order is a rank
+ * sort of each of runs [n_runs][2] int64 = (start, length <= CIM_VOC_MAX_RUN) - the runs tile [0, D) and none crosses a
+ * class - followed by the bottom-up merge rounds of cim_segm_accumulate (jobs, round_off, rounds: the same arrays, over the
+ * runs).  Then cumulative tp / fp, rec = tp / npos, prec = tp / max(tp + fp, DBL_EPSILON), written in sorted order at the
+ * class's offsets, and ap [K]: with thr11 != NULL the 11-point form over the host's 11 fp64 thresholds (ap = ap + p / 11. in
+ * their order), with thr11 == NULL the area form (precision envelope from the right, the sum of (mrec[i + 1] - mrec[i])
+ * mpre[i + 1] where recall changes; the sum's order differs from NumPy's pairwise one).  A class without
+ * detections: ap = 0; npos = 0: IEEE division (NaN recall: ap = 0 in the 11-point form, NaN in the area form).
+ * ws: cim_voc_ap_ws_bytes(D) bytes, 8-byte aligned.  One memset and 2 + rounds launches.
+ * None of the three allocates, synchronises or keeps state.  Whatever the box, confidence, flag, group, run and class_off
+ * arrays hold, nothing is read or written out of range; round_off and jobs are trusted as an index structure (round_off
+ * ascending within the jobs array, as cim_segm_accumulate trusts them), while a job that does not lie inside [0, D) moves nothing. */
+#define CIM_VOC_MAX_RUN 256             /* detections per run of cim_voc_ap */
+long long cim_box_image_ws_bytes(int D, int G, long long pairs);
+int cim_box_eval_image(const double* dt_box, int D, const double* gt_box, int G, const float* dt_score, const int32_t* meta,
+                       int n_groups, int n_dl, int n_gl, long long pairs, const double* gt_area, const int64_t* gt_id,
+                       const double* iou_thrs, int T, const double* area_rng, int A, void* ws, void* records, void* stream);
+int cim_voc_match(const double* dt_box, const double* dt_conf, int D, const double* gt_box, const uint8_t* gt_difficult, int G,
+                  const int32_t* groups, int n_groups, double ovthresh, int mode, uint8_t* tp, uint8_t* fp, double* ovmax,
+                  int32_t* jmax, void* stream);
+long long cim_voc_ap_ws_bytes(long long D);
+int cim_voc_ap(const double* dt_conf, const uint8_t* tp, const uint8_t* fp, long long D, const int64_t* class_off,
+               const double* npos, int K, const int64_t* runs, int n_runs, const int64_t* jobs, const int64_t* round_off,
+               int rounds, const double* thr11, void* ws, double* rec, double* prec, double* ap, void* stream);
 
 /* ------------------------------------------------------------------ training inputs from proposal masks (ABI-16 addition)
  * Replaces tools/pre/generate_7_7_{voc,coco}.py:35-42 (tight boxes, PIL nearest resize to S x S) and the label assignment of
