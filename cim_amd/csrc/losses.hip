@@ -665,7 +665,10 @@ __global__ __launch_bounds__(256) void loss_grad_combine_kernel(const float* __r
 // total = ((bag + pcl) + cls) + 3 iou  (model_builder.py:199 weights the IoU loss by 3; lib/utils/training_stats.py:72-83 adds
 // the four up in dictionary order for the backward pass) - one launch instead of a reduction, a scaling and the driver's
 // per-loss means and adds
+// (no contraction: the total is the sum of the four losses AS REPORTED, 3 iou rounded on its own like the reference's tensor - a
+// fused multiply-add gave a total one ulp off out[0] + out[1] + out[2] + out[4])
 __global__ void loss_finish_kernel(const float* __restrict__ part, int rows, float* __restrict__ out) {
+#pragma clang fp contract(off)
     const int k = threadIdx.x;
     float s = 0.0f;
     if (k < 4)
