@@ -82,6 +82,8 @@ SIGNATURES = {
     "cim_detect_ws_bytes": [c_int, c_int],
     "cim_detect_nms_limit": [_P, c_int, _P, c_int, c_int, c_float, c_float, c_int, _P, _P, _P, _P, _P],
     "cim_detect_corloc": [_P, c_int, c_int, c_int, _P, _P],
+    "cim_batch_detect_ws_bytes": [_P, c_int, c_int],
+    "cim_batch_detect_nms_limit": [_P, c_int, _P, _P, _P, c_int, c_int, c_float, c_float, c_int, _P, _P, _P, _P, _P, _P, _P],
     "cim_segm_words": [c_int, c_int],
     "cim_segm_pack": [_P, _P, c_longlong, c_int, c_int, c_int, _P, _P],
     "cim_segm_area": [_P, c_int, c_int, _P, _P],
@@ -144,7 +146,7 @@ def load():
 
 
 _LONG_RETURNING = {"cim_segm_rle_decode_ws_bytes", "cim_segm_image_ws_bytes", "cim_segm_record_bytes", "cim_segm_accumulate_ws_bytes", "cim_prop_ws_bytes", "cim_poly_ws_bytes", "cim_box_image_ws_bytes",
-                   "cim_voc_ap_ws_bytes"}
+                   "cim_voc_ap_ws_bytes", "cim_batch_detect_ws_bytes"}
 VALUE_RETURNING = _LONG_RETURNING | {"cim_segm_words"} | {"cim_maxpool2d_out_size", "cim_conv3x3_dx_parts", "cim_mining_sync_bytes", "cim_conv1x1_bwd_workspace", "cim_conv3x3_nchw_bwd_workspace", "cim_conv3x3_nchw_splits", "cim_gemm_small_splits", "cim_mining_lds_bytes", "cim_bn_act_bwd_chunks", "cim_gemm_pair_splits", "cim_roi_align_bwd_workspace", "cim_roi_align_bwd_scratch", "cim_detect_ws_bytes"}      # return a count, not a status
 
 

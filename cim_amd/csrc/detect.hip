@@ -17,6 +17,12 @@
 //                           the boxes, OR the matrix rows of the chunk's kept boxes into `removed`.
 //   detect_limit_kernel     one workgroup: compacts the kept bits in (class, proposal) order, finds the D-th largest kept
 //                           score by a radix select on the score bits, writes the records that reach it.
+//
+// The ragged batch form (cim_batch_detect_nms_limit) runs B images back to back in five launches: a
+// one-workgroup prologue (per-image words, tile / matrix / keep offsets from row_off), the overlap tiles of all images in a
+// 1-D grid (a binary search finds a tile's image), the NMS on a (C, B) grid, one limit workgroup per image, and the
+// compaction of the per-image records into one array.  Each per-image body below (overlap_tile, nms_class, limit_image) is
+// ONE __device__ function called by both forms with base pointers, so the exactness contract holds for both.
 #pragma clang fp contract(off)                      // (x2 - x1 + 1) * ... and iarea + area - w*h: no fused multiply-adds
 #include "common.h"
 #include "../../include/cim_hip.h"
@@ -33,21 +39,22 @@ __device__ __forceinline__ uint32_t orderable(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-__device__ int block_exclusive_scan(int v, int* part, int* total) {      // 1024 lanes; returns the exclusive prefix
+template <typename T>
+__device__ T block_exclusive_scan(T v, T* part, T* total) {              // 1024 lanes; returns the exclusive prefix
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int incl = v;
+    T incl = v;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
-        const int x = __shfl_up(incl, o);
+        const T x = __shfl_up(incl, o);
         if (lane >= o) incl += x;
     }
     __syncthreads();                                                     // (part[] of the previous scan has been read)
     if (lane == 63) part[wave] = incl;
     __syncthreads();
-    int woff = 0, tot = 0;
+    T woff = 0, tot = 0;
 #pragma unroll
     for (int w = 0; w < 16; ++w) {
-        const int p = part[w];
+        const T p = part[w];
         tot += p;
         woff += (w < wave) ? p : 0;
     }
@@ -75,12 +82,22 @@ __device__ __forceinline__ bool overlaps(float4 bi, float ai, float4 bj, float a
     return ovr >= thr;
 }
 
-__global__ __launch_bounds__(64) void detect_overlap_kernel(const float4* __restrict__ boxes, int N, int W, float thr,
-                                                            unsigned long long* __restrict__ mat) {
+// TEST.PROPOSAL_FILTER (tools/evaluation.py:108-115): the proposal's scores read as 0 when its area - no + 1, fp32 - is
+// > hi or < lo (both strict; bounds = {lo, hi} of the image, null: no filter)
+__device__ __forceinline__ bool filtered_out(const float4* box, const float* bounds) {
+    if (!bounds) return false;
+    const float4 b = *box;
+    const float a = (b.z - b.x) * (b.w - b.y);
+    return a > bounds[1] || a < bounds[0];
+}
+
+// one 64 x 64 tile (row block ib, column block jb) of one image's overlap matrix; one wave
+__device__ __forceinline__ void overlap_tile(const float4* __restrict__ boxes, int N, int W, float thr,
+                                             unsigned long long* __restrict__ mat, int jb, int ib) {
     __shared__ float4 s_box[64];
     __shared__ float s_area[64];
-    const int lane = threadIdx.x, jb = blockIdx.x;
-    const int j = jb * 64 + lane, i = blockIdx.y * 64 + lane;
+    const int lane = threadIdx.x;
+    const int j = jb * 64 + lane, i = ib * 64 + lane;
     if (j < N) {
         const float4 b = boxes[j];
         s_box[lane] = b;
@@ -97,21 +114,26 @@ __global__ __launch_bounds__(64) void detect_overlap_kernel(const float4* __rest
     mat[(size_t)i * W + jb] = bits;
 }
 
+__global__ __launch_bounds__(64) void detect_overlap_kernel(const float4* __restrict__ boxes, int N, int W, float thr,
+                                                            unsigned long long* __restrict__ mat) {
+    overlap_tile(boxes, N, W, thr, mat, blockIdx.x, blockIdx.y);
+}
+
 // keys: (orderable(score) << 32) | proposal, sorted descending = score descending, then HIGHER proposal index first
 // (np.argsort(s, kind="stable")[::-1]); 0 pads the sort (no candidate key is 0: candidates are never NaN)
-__global__ __launch_bounds__(1024) void detect_nms_kernel(const float* __restrict__ scores, int ld,
-                                                          const float4* __restrict__ boxes, int N, int W, float score_thr,
-                                                          float nms_thr, const unsigned long long* __restrict__ mat,
-                                                          unsigned long long* __restrict__ keepbits) {
-    extern __shared__ unsigned long long s_key[];                      // [pow2ceil(N)]
+// one class c of one image: kc = the class's W words of kept bits; s_key = the workgroup's dynamic LDS [pow2ceil(N)]
+__device__ __forceinline__ void nms_class(const float* __restrict__ scores, int ld, const float4* __restrict__ boxes, int N,
+                                          int W, float score_thr, float nms_thr,
+                                          const unsigned long long* __restrict__ mat, unsigned long long* __restrict__ kc,
+                                          int c, const float* __restrict__ bounds, unsigned long long* s_key) {
     __shared__ int s_cnt;
-    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x, lane = tid & 63;
     if (tid == 0) s_cnt = 0;
     __syncthreads();
     // test.py:370 / mask_eval_utils.py:62: s > float32(SCORE_THRESH); the order of insertion does not matter (keys are unique)
     for (int base = 0; base < N; base += 1024) {
         const int p = base + tid;
-        const float s = p < N ? scores[(size_t)p * ld + c] : 0.0f;
+        const float s = p < N && !filtered_out(boxes + p, bounds) ? scores[(size_t)p * ld + c] : 0.0f;
         const bool cand = p < N && s > score_thr;
         const unsigned long long b = __ballot(cand);
         int at = 0;
@@ -182,18 +204,27 @@ __global__ __launch_bounds__(1024) void detect_nms_kernel(const float* __restric
             }
         }
     }
-    unsigned long long* kc = keepbits + (size_t)c * W;
     if (lane < W) kc[lane] = kb0;
     if (lane + 64 < W) kc[lane + 64] = kb1;
 }
 
+__global__ __launch_bounds__(1024) void detect_nms_kernel(const float* __restrict__ scores, int ld,
+                                                          const float4* __restrict__ boxes, int N, int W, float score_thr,
+                                                          float nms_thr, const unsigned long long* __restrict__ mat,
+                                                          unsigned long long* __restrict__ keepbits) {
+    extern __shared__ unsigned long long s_key[];                      // [pow2ceil(N)]
+    const int c = blockIdx.x;
+    nms_class(scores, ld, boxes, N, W, score_thr, nms_thr, mat, keepbits + (size_t)c * W, c, nullptr, s_key);
+}
+
 // test.py:395-403: the kept set in (class, proposal) order, thresholded at the max_det-th largest kept score when more
-// than max_det are kept.  det records: (proposal, class, score bits)
-__global__ __launch_bounds__(1024) void detect_limit_kernel(const float* __restrict__ scores, int ld, int C, int W,
-                                                            int max_det, const unsigned long long* __restrict__ keepbits,
-                                                            uint32_t* __restrict__ lkey, int* __restrict__ lidx,
-                                                            int* __restrict__ lcls, int* __restrict__ det,
-                                                            int* __restrict__ count, int* __restrict__ total) {
+// than max_det are kept.  det records: (proposal, class, score bits).  cmask [C] (null: every class): classes whose
+// records are written - applied AFTER the limit (generate_mask_for_MaskRCNN.py:124-136 limits over all classes first)
+__device__ __forceinline__ void limit_image(const float* __restrict__ scores, int ld, int C, int W, int max_det,
+                                            const unsigned long long* __restrict__ keepbits, uint32_t* __restrict__ lkey,
+                                            int* __restrict__ lidx, int* __restrict__ lcls, int* __restrict__ det,
+                                            int* __restrict__ count, int* __restrict__ total,
+                                            const unsigned char* __restrict__ cmask) {
     __shared__ int s_part[16];
     __shared__ unsigned s_hist[256];
     __shared__ unsigned s_prefix, s_k;
@@ -255,7 +286,7 @@ __global__ __launch_bounds__(1024) void detect_limit_kernel(const float* __restr
     int outn = 0;
     for (int base = 0; base < T; base += 1024) {
         const int i = base + tid;
-        const bool on = i < T && lkey[i] >= thr_key;
+        const bool on = i < T && lkey[i] >= thr_key && (!cmask || cmask[lcls[i]]);
         int tot;
         const int o = outn + block_exclusive_scan(on ? 1 : 0, s_part, &tot);
         if (on) {
@@ -268,6 +299,167 @@ __global__ __launch_bounds__(1024) void detect_limit_kernel(const float* __restr
         outn += tot;
     }
     if (tid == 0) *total = outn;
+}
+
+__global__ __launch_bounds__(1024) void detect_limit_kernel(const float* __restrict__ scores, int ld, int C, int W,
+                                                            int max_det, const unsigned long long* __restrict__ keepbits,
+                                                            uint32_t* __restrict__ lkey, int* __restrict__ lidx,
+                                                            int* __restrict__ lcls, int* __restrict__ det,
+                                                            int* __restrict__ count, int* __restrict__ total) {
+    limit_image(scores, ld, C, W, max_det, keepbits, lkey, lidx, lcls, det, count, total, nullptr);
+}
+
+// ---------------------------------------------------------------- ragged batch: B images back to back
+// Workspace head (BatchView): what the prologue derives from row_off on the device.  ok = 0 when the device's
+// row_off does not give the totals the host sized the grids and the workspace with: every later launch then does nothing
+// and total[b] = -1.
+struct BatchView {
+    int* ok;                    // [1]
+    int* start;                 // [B]      first row of image b
+    int* n;                     // [B]      N_b
+    int* words;                 // [B]      W_b = ceil(N_b / 64)
+    int* word_off;              // [B + 1]  prefix of W_b (keep bits: C * word_off[b] words before image b)
+    int* tile_off;              // [B + 1]  prefix of W_b^2
+    long long* mat_off;         // [B + 1]  prefix of N_b * W_b (u64 words)
+};
+
+__host__ __device__ inline size_t batch_meta_bytes(int B) {
+    return ((((size_t)2 + 3 * (size_t)B + 2 * ((size_t)B + 1)) * 4 + 7) & ~(size_t)7) + ((size_t)B + 1) * 8;
+}
+
+__host__ __device__ inline BatchView batch_view(void* ws, int B) {
+    BatchView v;
+    int* p = static_cast<int*>(ws);
+    v.ok = p;
+    v.start = p + 2;
+    v.n = v.start + B;
+    v.words = v.n + B;
+    v.word_off = v.words + B;
+    v.tile_off = v.word_off + B + 1;
+    v.mat_off = reinterpret_cast<long long*>(static_cast<char*>(ws) + batch_meta_bytes(B) - ((size_t)B + 1) * 8);
+    return v;
+}
+
+__global__ __launch_bounds__(1024) void detect_batch_prologue_kernel(const int* __restrict__ row_off, int B, int total_n,
+                                                                     int tot_words, int tot_tiles, long long tot_mat,
+                                                                     void* ws) {
+    __shared__ int s_part[16];
+    __shared__ long long s_lpart[16];
+    __shared__ int s_bad;
+    const BatchView v = batch_view(ws, B);
+    const int tid = threadIdx.x;
+    if (tid == 0) s_bad = (row_off[0] != 0 || row_off[B] != total_n) ? 1 : 0;
+    __syncthreads();
+    int words = 0, tiles = 0;
+    long long mat = 0;
+    for (int base = 0; base < B; base += 1024) {
+        const int b = base + tid;
+        int s = 0, n = 0;
+        if (b < B) {
+            s = row_off[b];
+            n = row_off[b + 1] - s;
+            if (s < 0 || n < 1 || n > kMaxN || s > total_n - n) {
+                atomicOr(&s_bad, 1);
+                s = 0;
+                n = 1;
+            }
+        }
+        const int W = (n + 63) / 64;                                   // (0 past the last image)
+        int tw, tt;
+        long long tm;
+        const int ow = words + block_exclusive_scan(W, s_part, &tw);
+        const int ot = tiles + block_exclusive_scan(W * W, s_part, &tt);
+        const long long om = mat + block_exclusive_scan((long long)n * W, s_lpart, &tm);
+        if (b < B) {
+            v.start[b] = s;
+            v.n[b] = n;
+            v.words[b] = W;
+            v.word_off[b] = ow;
+            v.tile_off[b] = ot;
+            v.mat_off[b] = om;
+        }
+        words += tw;
+        tiles += tt;
+        mat += tm;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        v.word_off[B] = words;
+        v.tile_off[B] = tiles;
+        v.mat_off[B] = mat;
+        *v.ok = (!s_bad && words == tot_words && tiles == tot_tiles && mat == tot_mat) ? 1 : 0;
+    }
+}
+
+__global__ __launch_bounds__(64) void detect_batch_overlap_kernel(const float4* __restrict__ boxes, int B, float thr,
+                                                                  void* ws, unsigned long long* __restrict__ mat) {
+    const BatchView v = batch_view(ws, B);
+    if (!*v.ok) return;
+    const int t = blockIdx.x;                                          // < tile_off[B]: the grid is sized by it
+    int lo = 0, hi = B - 1;                                            // the last image with tile_off[b] <= t
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (v.tile_off[mid] <= t) lo = mid;
+        else hi = mid - 1;
+    }
+    const int W = v.words[lo], local = t - v.tile_off[lo];
+    if (local >= W * W) return;
+    overlap_tile(boxes + v.start[lo], v.n[lo], W, thr, mat + v.mat_off[lo], local % W, local / W);
+}
+
+__global__ __launch_bounds__(1024) void detect_batch_nms_kernel(const float* __restrict__ scores, int ld,
+                                                                const float4* __restrict__ boxes, int B, int C,
+                                                                float score_thr, float nms_thr,
+                                                                const float* __restrict__ area_bounds, void* ws,
+                                                                const unsigned long long* __restrict__ mat,
+                                                                unsigned long long* __restrict__ keepbits) {
+    extern __shared__ unsigned long long s_key[];                      // [pow2ceil(max N_b)]
+    const BatchView v = batch_view(ws, B);
+    if (!*v.ok) return;
+    const int c = blockIdx.x, b = blockIdx.y;
+    const int s = v.start[b], W = v.words[b];
+    nms_class(scores + (size_t)s * ld, ld, boxes + s, v.n[b], W, score_thr, nms_thr, mat + v.mat_off[b],
+              keepbits + (size_t)C * v.word_off[b] + (size_t)c * W, c, area_bounds ? area_bounds + 2 * b : nullptr, s_key);
+}
+
+// image b's scratch and records start at element C * start[b] of lkey / lidx / lcls and record C * start[b] of det_img
+__global__ __launch_bounds__(1024) void detect_batch_limit_kernel(const float* __restrict__ scores, int ld, int B, int C,
+                                                                  int max_det, const unsigned char* __restrict__ class_mask,
+                                                                  void* ws, const unsigned long long* __restrict__ keepbits,
+                                                                  uint32_t* __restrict__ lkey, int* __restrict__ lidx,
+                                                                  int* __restrict__ lcls, int* __restrict__ det_img,
+                                                                  int* __restrict__ count, int* __restrict__ total) {
+    const BatchView v = batch_view(ws, B);
+    const int b = blockIdx.x;
+    if (!*v.ok) {
+        if (threadIdx.x == 0) total[b] = -1;
+        return;
+    }
+    const int s = v.start[b];
+    const size_t e = (size_t)C * s;
+    limit_image(scores + (size_t)s * ld, ld, C, v.words[b], max_det, keepbits + (size_t)C * v.word_off[b], lkey + e, lidx + e,
+                lcls + e, det_img + 3 * e, count + (size_t)b * C, total + b, class_mask ? class_mask + (size_t)b * C : nullptr);
+}
+
+// records of all images into one array, (image, class, proposal) order: image b's go to record sum(total[0 .. b))
+__global__ __launch_bounds__(256) void detect_batch_compact_kernel(int B, int C, void* ws, const int* __restrict__ det_img,
+                                                                   const int* __restrict__ total, int* __restrict__ det) {
+    __shared__ long long s_sum[256];
+    const BatchView v = batch_view(ws, B);
+    if (!*v.ok) return;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    long long acc = 0;
+    for (int i = tid; i < b; i += 256) acc += total[i];
+    s_sum[tid] = acc;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) s_sum[tid] += s_sum[tid + h];
+        __syncthreads();
+    }
+    const int* src = det_img + 3 * (size_t)C * v.start[b];
+    int* dst = det + 3 * (size_t)s_sum[0];
+    const int n = 3 * total[b];
+    for (int i = tid; i < n; i += 256) dst[i] = src[i];
 }
 
 // test.py:336-338: np.argmax(scores[:, j]) - the first index of the maximum, the first NaN if there is one
@@ -364,6 +556,120 @@ extern "C" int cim_detect_nms_limit(const float* scores, int ld, const float* bo
     hipLaunchKernelGGL(detect_limit_kernel, dim3(1), dim3(1024), 0, st, scores, ld, C, W, max_det, keep,
                        reinterpret_cast<uint32_t*>(w + L.lkey), reinterpret_cast<int*>(w + L.lidx),
                        reinterpret_cast<int*>(w + L.lcls), det, count_per_class, total);
+    CIM_CHECK_LAUNCH();
+    return 0;
+}
+
+namespace {
+
+struct BatchLayout {
+    size_t mat, keep, lkey, lidx, lcls, det_img, total;
+    int total_n, tot_words, tot_tiles, max_n;
+    long long tot_mat;
+};
+
+// false (with the error set) unless 1 <= B <= the image limit, row_off starts at 0, every 1 <= N_b <= CIM_DETECT_MAX_N and
+// 3 * C * sum N < 2^31
+bool batch_layout(const char* who, const int* row_off, int B, int C, BatchLayout* L) {
+    const char* limits = "need 1 <= B <= %d images, row_off[0] = 0 and non-decreasing, each 1 <= N_b <= %d, C >= 1 and "
+                         "3 * C * sum N < 2^31";
+    char why[256];
+    snprintf(why, sizeof why, limits, CIM_BATCH_DETECT_MAX_IMAGES, kMaxN);
+    if (!row_off) {
+        cim::set_error("%s: row_off (host) is null; %s", who, why);
+        return false;
+    }
+    if (B < 1 || B > CIM_BATCH_DETECT_MAX_IMAGES || C < 1) {
+        cim::set_error("%s: %s (B=%d, C=%d)", who, why, B, C);
+        return false;
+    }
+    if (row_off[0] != 0) {
+        cim::set_error("%s: %s (row_off[0]=%d)", who, why, row_off[0]);
+        return false;
+    }
+    long long words = 0, tiles = 0, mat = 0;
+    int max_n = 0;
+    for (int b = 0; b < B; ++b) {
+        const long long n = (long long)row_off[b + 1] - row_off[b];
+        if (n < 1 || n > kMaxN) {
+            cim::set_error("%s: %s (image %d: row_off %d -> %d, N_b=%lld)", who, why, b, row_off[b], row_off[b + 1], n);
+            return false;
+        }
+        const long long W = (n + 63) / 64;
+        words += W;
+        tiles += W * W;
+        mat += n * W;
+        if (n > max_n) max_n = (int)n;
+    }
+    const long long cap = (long long)C * row_off[B];
+    if (cap > (long long)(INT_MAX / 3)) {
+        cim::set_error("%s: %s (C=%d, sum N=%d)", who, why, C, row_off[B]);
+        return false;
+    }
+    const size_t ints = ((size_t)cap * 4 + 255) & ~(size_t)255;
+    L->total_n = row_off[B];
+    L->tot_words = (int)words;                                         // <= B * 128
+    L->tot_tiles = (int)tiles;                                         // <= B * 128^2 < 2^31 at the image limit
+    L->tot_mat = mat;
+    L->max_n = max_n;
+    L->mat = (batch_meta_bytes(B) + 255) & ~(size_t)255;
+    L->keep = L->mat + (size_t)mat * 8;
+    L->lkey = L->keep + (size_t)C * (size_t)words * 8;
+    L->lidx = L->lkey + ints;
+    L->lcls = L->lidx + ints;
+    L->det_img = L->lcls + ints;
+    L->total = L->det_img + 3 * ints;
+    return true;
+}
+
+}  // namespace
+
+extern "C" long long cim_batch_detect_ws_bytes(const int* row_off, int B, int C) {
+    BatchLayout L;
+    if (!batch_layout("cim_batch_detect_ws_bytes", row_off, B, C, &L)) return -1;
+    return (long long)L.total;
+}
+
+extern "C" int cim_batch_detect_nms_limit(const float* scores, int ld, const float* boxes, const int* row_off_dev,
+                                          const int* row_off_host, int B, int C, float score_thr, float nms_thr, int max_det,
+                                          const float* area_bounds, const unsigned char* class_mask, void* ws, int* det,
+                                          int* count, int* total, void* stream) {
+    BatchLayout L;
+    if (!batch_layout("cim_batch_detect_nms_limit", row_off_host, B, C, &L)) return -1;
+    if (ld < C) {
+        cim::set_error("cim_batch_detect_nms_limit: the scores' leading dimension must be >= C (ld=%d, C=%d)", ld, C);
+        return -1;
+    }
+    if (area_bounds && !(score_thr >= 0.0f)) {                         // a filtered score reads 0: it must not be a candidate
+        cim::set_error("cim_batch_detect_nms_limit: area_bounds needs score_thr >= 0 (score_thr=%g)", (double)score_thr);
+        return -1;
+    }
+    CIM_CHECK_ARG(scores && boxes && row_off_dev && ws && det && count && total);
+    CIM_CHECK_ARG(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)ws & 7) == 0);
+    hipStream_t st = cim::as_stream(stream);
+    char* w = static_cast<char*>(ws);
+    auto* mat = reinterpret_cast<unsigned long long*>(w + L.mat);
+    auto* keep = reinterpret_cast<unsigned long long*>(w + L.keep);
+    int* det_img = reinterpret_cast<int*>(w + L.det_img);
+    const float4* bx = reinterpret_cast<const float4*>(boxes);
+    hipLaunchKernelGGL(detect_batch_prologue_kernel, dim3(1), dim3(1024), 0, st, row_off_dev, B, L.total_n, L.tot_words,
+                       L.tot_tiles, L.tot_mat, ws);
+    CIM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(detect_batch_overlap_kernel, dim3(L.tot_tiles), dim3(64), 0, st, bx, B, nms_thr, ws, mat);
+    CIM_CHECK_LAUNCH();
+    int P = 1;
+    while (P < L.max_n) P <<= 1;
+    const int lds = P * 8;
+    CIM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(detect_batch_nms_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL(detect_batch_nms_kernel, dim3(C, B), dim3(1024), lds, st, scores, ld, bx, B, C, score_thr, nms_thr,
+                       area_bounds, ws, mat, keep);
+    CIM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(detect_batch_limit_kernel, dim3(B), dim3(1024), 0, st, scores, ld, B, C, max_det, class_mask, ws, keep,
+                       reinterpret_cast<uint32_t*>(w + L.lkey), reinterpret_cast<int*>(w + L.lidx),
+                       reinterpret_cast<int*>(w + L.lcls), det_img, count, total);
+    CIM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(detect_batch_compact_kernel, dim3(B), dim3(256), 0, st, B, C, ws, det_img, total, det);
     CIM_CHECK_LAUNCH();
     return 0;
 }

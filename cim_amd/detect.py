@@ -14,6 +14,7 @@ import torch
 from . import _lib
 
 MAX_N = 8192                    # CIM_DETECT_MAX_N of include/cim_hip.h
+MAX_IMAGES = 4096               # CIM_BATCH_DETECT_MAX_IMAGES: images of one batched call
 
 # device results: views of ONE int32 buffer [total | count_per_class[C] | det[C * N][3]] so that the host copy is one slice
 Detections = collections.namedtuple("Detections", "buf num_classes max_det")
@@ -79,6 +80,157 @@ def to_host(det):
         h = np.concatenate([h, det.buf[head + 3 * first:head + 3 * total].cpu().numpy()])
     rec = h[head:head + 3 * total].reshape(total, 3)
     return (rec[:, 0].astype(np.int64), rec[:, 1].copy(), rec[:, 2].view(np.float32).copy(), h[1:head].copy())
+
+
+def _batch_parts(x, what):
+    """A per-image list or one concatenated array - device tensors or NumPy arrays - as (parts, rows per part); float32 is
+    demanded of scores here, before anything is uploaded."""
+    parts = list(x) if isinstance(x, (list, tuple)) else [x]
+    if not parts:
+        raise ValueError("cim_amd.detect: no images")
+    for a in parts:
+        if torch.is_tensor(a) and not a.is_cuda:
+            raise _lib.CimHipError("cim_amd.detect: %s must be CUDA/HIP tensors or NumPy arrays (no CPU fallback)" % what)
+    parts = [a if torch.is_tensor(a) else np.asarray(a) for a in parts]
+    if what == "scores":
+        for a in parts:
+            if a.dtype not in (torch.float32, np.float32):
+                raise TypeError("cim_amd.detect: scores must be float32 (the reference compares fp32 scores), got %s" % a.dtype)
+    return parts, [int(a.shape[0]) for a in parts]
+
+
+def _batch_cat(parts):
+    """The parts back to back as ONE device tensor."""
+    if all(torch.is_tensor(a) for a in parts):
+        return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+    host = [a.cpu().numpy() if torch.is_tensor(a) else a for a in parts]
+    return torch.from_numpy(np.ascontiguousarray(np.concatenate(host, 0))).to(_device())
+
+
+def _per_image(x, B, cols, dtype, what, dev):
+    """Optional [B, cols] per-image argument (NumPy or device tensor) -> contiguous device tensor, or None."""
+    if x is None:
+        return None
+    if torch.is_tensor(x):
+        if not x.is_cuda:
+            raise _lib.CimHipError("cim_amd.detect: %s must be a CUDA/HIP tensor or a NumPy array (no CPU fallback)" % what)
+        t = x.to(dev, dtype).contiguous()
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype={torch.float32: np.float32, torch.uint8: np.uint8}[dtype])).to(dev)
+    if tuple(t.shape) != (B, cols):
+        raise ValueError("cim_amd.detect: %s must be [%d, %d], got %s" % (what, B, cols, tuple(t.shape)))
+    return t
+
+
+def _image_bytes(n, C):
+    """Workspace + output bytes one image of n proposals adds to a batched call (include/cim_hip.h; alignment aside)."""
+    W = (n + 63) // 64
+    return n * W * 8 + C * W * 8 + 9 * C * n * 4 + 28 + 4 * (1 + C)
+
+
+def _chunks(row_off, C, ws_budget_bytes):
+    """Consecutive images [i0, i1) per library call: workspace + output within the budget, the library's limits on B and
+    3 * C * sum N."""
+    B = len(row_off) - 1
+    cost = np.array([_image_bytes(int(n), C) for n in np.diff(row_off)], dtype=np.int64)
+    if cost.max() + 4096 > ws_budget_bytes:
+        raise ValueError("cim_amd.detect: ws_budget_bytes = %d does not hold one image (%d bytes)" % (ws_budget_bytes, cost.max() + 4096))
+    chunks, i0 = [], 0
+    while i0 < B:
+        i1, used = i0, 4096
+        while (i1 < B and i1 - i0 < MAX_IMAGES and used + cost[i1] <= ws_budget_bytes
+               and 3 * C * (row_off[i1 + 1] - row_off[i0]) < 2 ** 31):
+            used += cost[i1]
+            i1 += 1
+        if i1 == i0:
+            raise ValueError("cim_amd.detect: image %d: 3 * C * N reaches 2^31" % i0)
+        chunks.append((i0, i1))
+        i0 = i1
+    return chunks
+
+
+def nms_limit_batch(scores, boxes, score_thr=1e-5, nms_thr=0.3, max_det=100, num_classes=None, area_bounds=None,
+                    class_mask=None, ws_budget_bytes=1 << 30):
+    """`nms_limit` for many images in a few launches (csrc/detect.hip's ragged batch form).
+
+    scores / boxes: a list of per-image [N_b, C] / [N_b, 4] arrays (device tensors or NumPy), or scores = (concatenated
+    [sum N, C], row_off [B + 1]) with boxes the concatenated [sum N, 4].  One score_thr, nms_thr, max_det for all images.
+    area_bounds [B, 2] f32 = (lo_b, hi_b): TEST.PROPOSAL_FILTER - a proposal whose (x2 - x1) * (y2 - y1) is > hi_b or < lo_b
+    scores 0 in every class (tools/evaluation.py:108-115; the caller passes float32(0.00002 * area), float32(0.85 * area)).
+    class_mask [B, C] u8: classes whose records are returned, applied AFTER the limit over all classes.
+
+    The images are split into chunks whose workspace plus output fits ws_budget_bytes (at most MAX_IMAGES images each); each
+    chunk is one library call and one device-to-host copy of its header and records (a second only when ties at the limit
+    keep more than max_det in an image, or without a limit).  Launches on the current stream.  Returns host arrays
+    (image int64 [T], idx int64 [T], cls int32 [T], score f32 [T], count int32 [B, C]), records in (image, class, proposal)
+    order."""
+    if isinstance(scores, tuple) and len(scores) == 2 and np.ndim(scores[1]) == 1 and np.ndim(scores[0]) == 2:
+        sp, _ = _batch_parts(scores[0], "scores")
+        bp, _ = _batch_parts(boxes, "boxes")
+        row_off = np.asarray(scores[1].cpu() if torch.is_tensor(scores[1]) else scores[1], dtype=np.int64)
+    else:
+        sp, rows = _batch_parts(scores, "scores")
+        bp, brows = _batch_parts(boxes, "boxes")
+        if rows != brows:
+            raise ValueError("cim_amd.detect: scores and boxes disagree on the proposals per image")
+        row_off = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+    sc, bx = _batch_cat(sp), _batch_cat(bp)
+    if sc.dim() != 2:
+        raise ValueError("cim_amd.detect: scores must be [sum N, C], got %s" % (tuple(sc.shape),))
+    total_n, cols = sc.shape
+    C = cols if num_classes is None else int(num_classes)
+    if not 1 <= C <= cols:
+        raise ValueError("cim_amd.detect: %d classes asked of a [%d, %d] score array" % (C, total_n, cols))
+    B = row_off.size - 1
+    n_b = np.diff(row_off)
+    if B < 1 or row_off[0] != 0 or row_off[-1] != total_n or n_b.min() < 1 or n_b.max() > MAX_N:
+        raise ValueError("cim_amd.detect: row_off must run from 0 to %d with 1 <= N_b <= %d proposals per image" % (total_n, MAX_N))
+    if tuple(bx.shape) != (total_n, 4) or bx.device != sc.device:
+        raise ValueError("cim_amd.detect: boxes must be [%d, 4] on %s, got %s on %s" % (total_n, sc.device, tuple(bx.shape), bx.device))
+    if sc.stride(1) != 1 or sc.stride(0) < C:
+        sc = sc.contiguous()
+    bx = bx.to(torch.float32).contiguous()
+    dev = sc.device
+    bounds = _per_image(area_bounds, B, 2, torch.float32, "area_bounds", dev)
+    cmask = _per_image(class_mask, B, C, torch.uint8, "class_mask", dev)
+    max_det = int(max_det)
+
+    chunks = _chunks(row_off, C, ws_budget_bytes)
+
+    out_img, out_idx, out_cls, out_sc = [], [], [], []
+    count = np.zeros((B, C), np.int32)
+    for i0, i1 in chunks:
+        nb, r0, r1 = i1 - i0, int(row_off[i0]), int(row_off[i1])
+        ro_h = np.ascontiguousarray(row_off[i0:i1 + 1] - r0, dtype=np.int32)
+        ws_bytes = _lib.call("cim_batch_detect_ws_bytes", ro_h.ctypes.data, nb, C)
+        if ws_bytes < 0:
+            raise ValueError(_lib.load().cim_last_error().decode())
+        ro_d = torch.from_numpy(ro_h).pin_memory().to(dev, non_blocking=True)
+        ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
+        head = nb * (1 + C)
+        cap = C * (r1 - r0)
+        buf = torch.empty(head + 3 * cap, dtype=torch.int32, device=dev)          # [total[nb] | count[nb, C] | det[cap][3]]
+        s_c, b_c = sc[r0:r1], bx[r0:r1]
+        base = buf.data_ptr()
+        _lib.call("cim_batch_detect_nms_limit", s_c.data_ptr(), sc.stride(0), b_c.data_ptr(), ro_d.data_ptr(), ro_h.ctypes.data,
+                  nb, C, float(score_thr), float(nms_thr), max_det, None if bounds is None else bounds[i0:i1].data_ptr(),
+                  None if cmask is None else cmask[i0:i1].data_ptr(), ws.data_ptr(), base + 4 * head, base + 4 * nb, base,
+                  _lib.stream_ptr())
+        first = min(cap, nb * max_det) if max_det > 0 else 0
+        h = buf[:head + 3 * first].cpu().numpy()
+        tot = h[:nb].astype(np.int64)
+        if tot.min() < 0:
+            raise _lib.CimHipError("cim_amd.detect: the device's row_off disagrees with the host's")
+        T = int(tot.sum())
+        if T > first:
+            h = np.concatenate([h, buf[head + 3 * first:head + 3 * T].cpu().numpy()])
+        rec = h[head:head + 3 * T].reshape(T, 3)
+        count[i0:i1] = h[nb:head].reshape(nb, C)
+        out_img.append(np.repeat(np.arange(i0, i1, dtype=np.int64), tot))
+        out_idx.append(rec[:, 0].astype(np.int64))
+        out_cls.append(rec[:, 1].copy())
+        out_sc.append(rec[:, 2].view(np.float32).copy())
+    return (np.concatenate(out_img), np.concatenate(out_idx), np.concatenate(out_cls), np.concatenate(out_sc), count)
 
 
 def corloc(scores, num_classes=None):

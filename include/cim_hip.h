@@ -259,6 +259,32 @@ int cim_detect_nms_limit(const float* scores, int ld, const float* boxes, int N,
  * any.  out [C][2] i32 = (proposal, score bit pattern).  Same shape limits as above. */
 int cim_detect_corloc(const float* scores, int ld, int N, int C, int32_t* out, void* stream);
 
+/* Ragged batch form (additive: cim_abi_version() stays 16): the same stage for B images in ONE call of five
+ * launches - a one-workgroup prologue (per-image words and offsets from row_off), the 64 x 64 overlap tiles of all images in
+ * a 1-D grid, the NMS on a (C, B) grid, one limit workgroup per image, and the compaction of the records.  Each per-image
+ * body is the device code of the single-image entry above, so its exactness contract and tie rule hold unchanged.
+ *
+ * scores [sum N, ld] f32 and boxes [sum N, 4] f32, the images back to back; row_off [B + 1] i32 (image b = rows
+ * row_off[b] .. row_off[b + 1]) twice: on the device (what the kernels read) and on the host (sizes the grids and the
+ * workspace, validates the shapes; the launches do nothing and total[b] = -1 if the two disagree).  One score_thr, nms_thr
+ * and max_det for the call.  Limits, refused before any launch (-1, cim_last_error() names them): 1 <= B <=
+ * CIM_BATCH_DETECT_MAX_IMAGES, row_off[0] = 0, every 1 <= N_b <= CIM_DETECT_MAX_N, C >= 1, 3 * C * sum N < 2^31, ld >= C.
+ *   area_bounds [B][2] f32 = (lo_b, hi_b) on the device, or NULL: TEST.PROPOSAL_FILTER (tools/evaluation.py:108-115) - a
+ *       proposal whose (x2 - x1) * (y2 - y1) (fp32, no + 1) is > hi_b or < lo_b has its score read as 0.0f for every class,
+ *       before the s > score_thr test; both compares are strict.  Needs score_thr >= 0 (a zero score is then no candidate).
+ *   class_mask [B][C] u8 on the device, or NULL: only classes with a nonzero entry are written - applied AFTER the limit
+ *       over all classes (tools/generate_mask_for_MaskRCNN.py:124-136), never before.
+ *   ws: cim_batch_detect_ws_bytes(row_off (host), B, C) bytes, 8-byte aligned, no initial content.
+ * Outputs: det [C * sum N][3] i32 records (proposal WITHIN its image, class, score bit pattern) of all images in one
+ * contiguous array, in (image, class ascending, proposal ascending) order - the first sum(total) are written;
+ * count [B][C] records per (image, class); total [B] records per image.  No allocation, no host copy, no synchronisation. */
+#define CIM_BATCH_DETECT_MAX_IMAGES 4096
+long long cim_batch_detect_ws_bytes(const int32_t* row_off_host, int B, int C);
+int cim_batch_detect_nms_limit(const float* scores, int ld, const float* boxes, const int32_t* row_off_dev,
+                               const int32_t* row_off_host, int B, int C, float score_thr, float nms_thr, int max_det,
+                               const float* area_bounds, const unsigned char* class_mask, void* ws, int32_t* det,
+                               int32_t* count, int32_t* total, void* stream);
+
 /* ------------------------------------------------------------------ instance-segmentation evaluation (ABI-16 addition)
  * Replaces pycocotools' mask.encode / decode / iou and COCOeval(..., 'segm').evaluateImg / accumulate as the reference runs
  * them (tools/evaluation.py:72-145, 236-241; lib/datasets/json_inference.py:24-55; lib/utils/mask_eval_utils.py:113-116).
