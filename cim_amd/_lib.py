@@ -3,119 +3,32 @@ library is missing or a call fails, this raises."""
 import ctypes
 import os
 
-from ctypes import c_float, c_int, c_longlong, c_void_p
+from . import _abi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # CIM_HIP_LIB: an ablation build (python -m cim_amd.build --out=...) for whole-step A/B runs; must export the same ABI
 LIB_PATH = os.environ.get("CIM_HIP_LIB") or os.path.join(HERE, "libcim_hip.so")
-
-# name -> argtypes (all return int)
-_P = c_void_p
-SIGNATURES = {
-    "cim_roi_align_fwd": [_P, _P, _P] + [c_int] * 6 + [c_float, c_int, c_int, _P],
-    "cim_roi_align_fwd_ws": [_P, _P, _P] + [c_int] * 6 + [c_float, c_int, c_int, _P, _P],
-    "cim_roi_align_maskcat_fwd_ws": [_P, _P, _P, _P] + [c_int] * 6 + [c_float, c_int, c_int, _P, _P],
-    "cim_roi_align_wino7_pair_fwd": [_P, _P, _P, _P, _P] + [c_int] * 7 + [c_float, c_int, c_int, _P, _P],
-    "cim_roi_align_bwd_ws": [_P, _P, _P] + [c_int] * 6 + [c_float, c_int, c_int, _P, c_int, _P, _P],
-    "cim_roi_align_maskcat_bwd_ws": [_P, _P, _P, _P] + [c_int] * 6 + [c_float, c_int, c_int, _P, c_int, _P, _P],
-    "cim_roi_align_bwd_workspace": [c_int, c_int, c_int, c_int],
-    "cim_roi_align_bwd_scratch": [c_int, c_int, c_int, c_int, c_int],
-    "cim_roi_align_bwd": [_P, _P, _P] + [c_int] * 6 + [c_float, c_int, c_int, _P, _P],
-    "cim_roi_align_maskcat_fwd": [_P, _P, _P, _P] + [c_int] * 6 + [c_float, c_int, c_int, _P],
-    "cim_roi_align_maskcat_bwd": [_P, _P, _P, _P] + [c_int] * 6 + [c_float, c_int, c_int, _P, _P],
-    "cim_roi_align_forms": [c_int] * 9 + [_P] * 3,
-    "cim_maxpool2d_out_size": [c_int, c_int, c_int, c_int],
-    "cim_maxpool2d_fwd": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],
-    "cim_maxpool2d_bwd": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],
-    "cim_upsample_nearest_fwd": [_P, _P, c_int, c_int, c_int, c_int, c_int, _P],
-    "cim_upsample_nearest_bwd": [_P, _P, c_int, c_int, c_int, c_int, _P],
-    "cim_image_prep": [_P, c_int, c_int, _P, c_int, c_int, c_longlong, c_int, ctypes.c_double, c_int, _P, _P],
-    "cim_mask_pack": [_P, _P, c_int, c_int, _P],
-    "cim_mask_iou_pair": [_P, c_int, c_int, _P, _P, _P, _P],
-    "cim_asy_flag": [_P, c_int, c_float, _P, _P],
-    "cim_asy_prep": [_P, c_int, _P, c_int, _P, _P, _P],
-    "cim_mining_step": [_P, _P, _P],
-    "cim_mining_lds_bytes": [c_int, c_int],
-    "cim_mining_sync_bytes": [],
-    "cim_gemm_small_splits": [c_int, c_int, c_int],
-    "cim_gemm_small_f32": [_P, _P, _P] + [c_int] * 8 + [_P, _P, _P, _P, _P, c_float, _P, c_int, c_int, _P, _P],
-    "cim_conv1x1_bwd_workspace": [c_int, c_int, c_int, c_int],
-    "cim_conv1x1_bn_act_bwd": [_P] * 8 + [c_float, c_int] + [_P] * 5 + [c_int] * 4 + [_P, _P, _P, _P, _P, c_int] + [c_int, _P, _P, c_float] + [_P] * 4 + [c_int],
-    "cim_bn_part_finish": [_P, c_int, _P],
-    "cim_conv3x3_nchw_splits": [c_int] * 5,
-    "cim_conv3x3_nchw_f32": [_P, _P, _P] + [c_int] * 6 + [_P, _P, _P, _P, _P, c_float, _P, c_int, c_int, _P, _P],
-    "cim_conv7x7_nchw_f32": [_P, _P, _P] + [c_int] * 5 + [_P, _P, _P, _P, c_float, c_int, _P],
-    "cim_conv3x3_nchw_bwd_workspace": [c_int] * 6,
-    "cim_conv3x3_dx_parts": [c_int] * 3,
-    "cim_conv3x3_nchw_bn_act_bwd": [_P] * 8 + [c_float, c_int] + [_P] * 5 + [c_int] * 7 + [_P, _P, _P, _P, _P, c_int] + [c_int, _P, _P, c_float] + [_P] * 4,
-    "cim_conv3x3_wt_multi": [_P, c_int, _P],
-    "cim_bn_act_fwd": [_P, _P, _P, _P, _P, _P, c_float, _P, c_int, c_int, c_int, c_int, _P],
-    "cim_bn_act_bwd_chunks": [c_int, c_int, c_int],
-    "cim_bn_act_bwd": [_P, _P, _P, _P, _P, _P, c_float, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
-    "cim_sgd_multi": [_P, _P, c_int, c_float, c_int, _P],
-    "cim_adam_multi": [_P, _P, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, _P],
-    "cim_gemm_pair_splits": [c_int, c_int, c_int],
-    "cim_gemm_pair": [_P, _P, _P, _P] + [c_int] * 6 + [c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, c_int, c_int, _P],
-    "cim_gemm_pair_batched": [_P, _P, _P] + [c_int] * 6 + [c_int, c_int, c_int, c_longlong, c_longlong, c_longlong,
-                              _P, _P, c_int, c_int, c_int, _P],
-    "cim_pair_scales": [_P, c_int, _P, _P, c_int, c_int, _P],
-    "cim_pair_split": [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_longlong, c_longlong, _P, _P, _P],
-    "cim_pair_amax": [_P, c_longlong, _P, _P],
-    "cim_pair_masked_stats": [_P, _P, c_int, c_int, _P, _P, _P],
-    "cim_wino7_flatten_bwd_dy_pair": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P],
-    "cim_wino7_pair_scales": [_P, c_int, _P, c_int, _P, _P],
-    "cim_wino7_input_pair": [_P, _P, _P, c_int, c_int, c_int, _P],
-    "cim_wino7_filter_pair": [_P, _P, _P, c_int, c_int, _P],
-    "cim_wino7_dy_pair": [_P, _P, _P, c_int, c_int, c_int, c_int, _P],
-    "cim_wino7_output_amax": [_P, _P, _P, c_int, c_int, c_int, _P, _P],
-    "cim_flatten_chw_pair": [_P, _P, _P, c_int, c_int, c_int, c_int, _P],
-    "cim_flatten_chw_bwd_bias": [_P, _P, _P, _P, c_int, c_int, c_int, _P],
-    "cim_wino_dx_adjoint_output": [_P, _P, c_int, c_int, c_int, c_int, _P],
-    "cim_wino7_dx_maskfold": [_P, _P, _P, c_int, c_int, _P],
-    "cim_wino_wgrad_output": [_P, _P, c_int, c_int, c_int, _P],
-    "cim_losses_fwd": [_P, _P],
-    "cim_linear_bias_f32": [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P],
-    "cim_loss_finish": [_P, c_int, _P, _P],
-    "cim_loss_grad_combine": [_P] * 8 + [c_int, c_int, c_int, _P],
-    "cim_head_act_fwd": [_P, _P, _P, c_int, c_int, c_int, _P],
-    "cim_head_act_bwd": [_P, _P, _P, _P, c_int, c_int, c_int, _P],
-    "cim_detect_ws_bytes": [c_int, c_int],
-    "cim_detect_nms_limit": [_P, c_int, _P, c_int, c_int, c_float, c_float, c_int, _P, _P, _P, _P, _P],
-    "cim_detect_corloc": [_P, c_int, c_int, c_int, _P, _P],
-    "cim_batch_detect_ws_bytes": [_P, c_int, c_int],
-    "cim_batch_detect_nms_limit": [_P, c_int, _P, _P, _P, c_int, c_int, c_float, c_float, c_int, _P, _P, _P, _P, _P, _P, _P],
-    "cim_segm_words": [c_int, c_int],
-    "cim_segm_pack": [_P, _P, c_longlong, c_int, c_int, c_int, _P, _P],
-    "cim_segm_area": [_P, c_int, c_int, _P, _P],
-    "cim_segm_rle_count": [_P, c_int, c_int, c_int, _P, _P],
-    "cim_segm_rle_write": [_P, c_int, c_int, c_int, _P, _P, _P, _P],
-    "cim_segm_rle_decode_ws_bytes": [c_longlong],
-    "cim_segm_rle_decode": [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P],
-    "cim_segm_image_ws_bytes": [c_int, c_int, c_longlong],
-    "cim_segm_record_bytes": [c_int, c_int, c_int, c_int],
-    "cim_segm_eval_image": [_P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_longlong, _P, _P, _P, c_int, _P, c_int,
-                            _P, _P, _P],
-    "cim_segm_accumulate_ws_bytes": [c_longlong, c_int, c_int, c_int],
-    "cim_segm_accumulate": [_P, c_int, c_longlong, c_int, _P, _P, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P,
-                            _P],
-    "cim_poly_ws_bytes": [c_int, c_int, c_int],
-    "cim_poly_fill": [_P, _P, _P, _P, c_int, c_int, c_longlong, c_int, c_int, c_int, _P, _P, _P],
-    "cim_box_image_ws_bytes": [c_int, c_int, c_longlong],
-    "cim_box_eval_image": [_P, c_int, _P, c_int, _P, _P, c_int, c_int, c_int, c_longlong, _P, _P, _P, c_int, _P, c_int, _P, _P, _P],
-    "cim_voc_match": [_P, _P, c_int, _P, _P, c_int, _P, c_int, ctypes.c_double, c_int, _P, _P, _P, _P, _P],
-    "cim_voc_ap_ws_bytes": [c_longlong],
-    "cim_voc_ap": [_P, _P, _P, c_longlong, _P, _P, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, _P],
-    "cim_prop_ws_bytes": [c_int, c_int, c_int],
-    "cim_prop_prepare": [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P],
-    "cim_prop_assign": [_P, _P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P],
-}
-
-ABI_VERSION = 16         # cim_abi_version() of include/cim_hip.h this binding was written against
-_lib = None
+HEADER = os.path.join(HERE, "..", "include", "cim_hip.h")       # (where cim_amd/build.py finds it)
 
 
 class CimHipError(RuntimeError):
     pass
+
+
+def parse_header(path):
+    """_abi.parse of a header file: (functions, structs, constants).  A missing header is an error like a missing library."""
+    if not os.path.exists(path):
+        raise CimHipError("C header %s not found: the ctypes binding is derived from it (there is no second copy of the ABI)" % path)
+    with open(path) as f:
+        return _abi.parse(f.read())
+
+
+# The binding IS the header: name -> (restype, argtypes), the `typedef struct`s as ctypes.Structure classes, the integer #defines
+FUNCTIONS, STRUCTS, CONSTANTS = parse_header(HEADER)
+SIGNATURES = {name: argtypes for name, (_, argtypes) in FUNCTIONS.items() if name not in ("cim_last_error", "cim_abi_version")}
+
+ABI_VERSION = 16         # cim_abi_version() of include/cim_hip.h this binding was written against
+_lib = None
 
 
 def load():
@@ -131,23 +44,22 @@ def load():
             "libcim_hip.so not found at %s - build it with `python -m cim_amd.build` "
             "(there is no CPU fallback for the CIM hot path)" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    lib.cim_last_error.restype = ctypes.c_char_p
-    lib.cim_last_error.argtypes = []
-    lib.cim_abi_version.restype = c_int
+    lib.cim_abi_version.restype, lib.cim_abi_version.argtypes = FUNCTIONS["cim_abi_version"]
     if lib.cim_abi_version() != ABI_VERSION:
         raise CimHipError("%s exports ABI %d, this package binds ABI %d: rebuild with `python -m cim_amd.build`"
                           % (LIB_PATH, lib.cim_abi_version(), ABI_VERSION))
-    for name, argtypes in SIGNATURES.items():
+    for name, (restype, argtypes) in FUNCTIONS.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing
-        fn.argtypes = argtypes
-        fn.restype = c_longlong if name in ("cim_conv1x1_bwd_workspace", "cim_conv3x3_nchw_bwd_workspace", "cim_roi_align_bwd_workspace", "cim_roi_align_bwd_scratch", "cim_mining_lds_bytes", "cim_mining_sync_bytes", "cim_detect_ws_bytes") or name in _LONG_RETURNING else c_int
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
 
-_LONG_RETURNING = {"cim_segm_rle_decode_ws_bytes", "cim_segm_image_ws_bytes", "cim_segm_record_bytes", "cim_segm_accumulate_ws_bytes", "cim_prop_ws_bytes", "cim_poly_ws_bytes", "cim_box_image_ws_bytes",
-                   "cim_voc_ap_ws_bytes", "cim_batch_detect_ws_bytes"}
-VALUE_RETURNING = _LONG_RETURNING | {"cim_segm_words"} | {"cim_maxpool2d_out_size", "cim_conv3x3_dx_parts", "cim_mining_sync_bytes", "cim_conv1x1_bwd_workspace", "cim_conv3x3_nchw_bwd_workspace", "cim_conv3x3_nchw_splits", "cim_gemm_small_splits", "cim_mining_lds_bytes", "cim_bn_act_bwd_chunks", "cim_gemm_pair_splits", "cim_roi_align_bwd_workspace", "cim_roi_align_bwd_scratch", "cim_detect_ws_bytes"}      # return a count, not a status
+# return a value, not a status: every `long long` entry point (byte counts) and the int entry points that return a count - which
+# no C type tells apart from a status, so they are named here (a name missing from this set fails loudly: call() raises on its value)
+VALUE_RETURNING = {name for name, (restype, _) in FUNCTIONS.items() if restype is ctypes.c_longlong} | {
+    "cim_bn_act_bwd_chunks", "cim_conv3x3_dx_parts", "cim_conv3x3_nchw_splits", "cim_gemm_pair_splits", "cim_gemm_small_splits",
+    "cim_maxpool2d_out_size", "cim_segm_words"}
 
 
 # split counts / workspace sizes of the body's layers: pure functions of their integer arguments (their tuning switches are read

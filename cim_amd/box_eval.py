@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from .segm_eval import MAX_DT, MAX_GT, SegmEvaluator, _err, _upload, merge_rounds, to_host  # noqa: F401
 
-MAX_RUN = 256                   # CIM_VOC_MAX_RUN of include/cim_hip.h
+MAX_RUN = _lib.CONSTANTS["CIM_VOC_MAX_RUN"]
 THR11 = np.arange(0., 1.1, 0.1)  # voc_ap's 11 recall thresholds: the host's fp64 values, never recomputed on the device
 
 

@@ -13,8 +13,8 @@ import torch
 
 from . import _lib
 
-MAX_N = 8192                    # CIM_DETECT_MAX_N of include/cim_hip.h
-MAX_IMAGES = 4096               # CIM_BATCH_DETECT_MAX_IMAGES: images of one batched call
+MAX_N = _lib.CONSTANTS["CIM_DETECT_MAX_N"]
+MAX_IMAGES = _lib.CONSTANTS["CIM_BATCH_DETECT_MAX_IMAGES"]         # images of one batched call
 
 # device results: views of ONE int32 buffer [total | count_per_class[C] | det[C * N][3]] so that the host copy is one slice
 Detections = collections.namedtuple("Detections", "buf num_classes max_det")

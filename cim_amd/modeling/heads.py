@@ -143,16 +143,7 @@ def PCL_loss(predict_cls, mat, labels):
 
 
 # --------------------------------------------------------------------------- fused losses (HIP)
-class _LossArgs(ctypes.Structure):
-    """Mirror of `cim_loss_args` in include/cim_hip.h."""
-    _fields_ = [("pc", ctypes.c_void_p), ("pd", ctypes.c_void_p),
-                ("rc", ctypes.c_void_p * 3), ("ri", ctypes.c_void_p * 3),
-                ("pseudo_labels", ctypes.c_void_p * 3), ("pseudo_iou_f16", ctypes.c_void_p * 3),
-                ("loss_weights", ctypes.c_void_p * 3), ("weight_scale", ctypes.c_float * 3),
-                ("layer_valid", ctypes.c_void_p), ("labels", ctypes.c_void_p),
-                ("mat", ctypes.c_void_p), ("status", ctypes.c_void_p),
-                ("N", ctypes.c_int), ("C1", ctypes.c_int), ("R", ctypes.c_int),
-                ("part", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("ld", ctypes.c_int)]
+_LossArgs = _lib.STRUCTS["cim_loss_args"]
 
 
 STATUS_BITS = {1: "a class produced more than K pseudo ground truths (internal)",
@@ -440,32 +431,9 @@ class HeadsFunction(torch.autograd.Function):
 
 
 # --------------------------------------------------------------------------- mining
-class _MiningLayer(ctypes.Structure):
-    """Mirror of `cim_mining_layer` in include/cim_hip.h."""
-    _P, _I, _F = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-    _fields_ = [("seed_score", _P), ("seed_ld", _I), ("seed_off", _I),
-                ("det", _P), ("det_ld", _I), ("det_off", _I), ("det_cs", _I),
-                ("wa", _P), ("wa_ld", _I), ("wa_off", _I),
-                ("wb", _P), ("wb_ld", _I), ("wb_off", _I), ("wb_cs", _I),
-                ("nms_thr", _F), ("cls_thr", _F), ("iou_thr", _F), ("con_thr", _F),
-                ("using_cim", _I), ("anti_noise", _I), ("flag_slot", _I), ("reserved_", _I),
-                ("topk", _P), ("seeds", _P), ("n_seeds", _P), ("res", _P),
-                ("gt_class", _P), ("gt_weight", _P), ("pre_idx", _P), ("pre_keep", _P),
-                ("gt_idx", _P), ("gt_cls", _P), ("gt_w", _P), ("counts", _P),
-                ("pseudo_labels", _P), ("pseudo_iou", _P), ("loss_weights", _P), ("max_idx", _P)]
-
-
-MAX_LAYERS = 4      # CIM_MAX_LAYERS
-
-
-class _MiningArgs(ctypes.Structure):
-    """Mirror of `cim_mining_args` in include/cim_hip.h."""
-    _P, _I = ctypes.c_void_p, ctypes.c_int32
-    _fields_ = [("N", _I), ("C", _I), ("K", _I), ("R", _I),
-                ("labels", _P), ("iou", _P), ("asy", _P), ("asy_t", _P), ("flags", _P), ("uniforms", _P),
-                ("max_uniforms", _I), ("reserved_", _I),
-                ("used", _P), ("status", _P), ("layer_valid", _P),
-                ("layer", _MiningLayer * MAX_LAYERS)]
+_MiningLayer = _lib.STRUCTS["cim_mining_layer"]
+_MiningArgs = _lib.STRUCTS["cim_mining_args"]
+MAX_LAYERS = _lib.CONSTANTS["CIM_MAX_LAYERS"]
 
 
 class _RngLedger:

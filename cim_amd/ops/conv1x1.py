@@ -8,7 +8,6 @@ BatchNorm frozen as :53-77 does.  The parameters stay the modules' own tensors (
 In NCHW the convolution of one image is W[Cout,Cin] . X[Cin,HW]: forward, data gradient (W^T . dY) and weight gradient
 (dY . X^T, split-K) are three layouts of the same small-tile fp32-MFMA GEMM; the BatchNorm backward stays the fused
 `bn_act` kernel.  CPU tensors, a BatchNorm in training mode or other convolution shapes take the ATen ops."""
-import ctypes
 import weakref
 
 import torch
@@ -132,9 +131,7 @@ def _receiver_runs(tok, node):
     return chain.node_runs(r() if r is not None else None) and not chain.restricted_pass(node)
 
 
-class _BnPartDesc(ctypes.Structure):          # cim_bn_part_desc of include/cim_hip.h
-    _fields_ = [("part", ctypes.c_void_p), ("var", ctypes.c_void_p), ("eps", ctypes.c_float), ("dgamma", ctypes.c_void_p),
-                ("dbeta", ctypes.c_void_p), ("images", ctypes.c_int), ("parts", ctypes.c_int), ("channels", ctypes.c_int)]
+_BnPartDesc = _lib.STRUCTS["cim_bn_part_desc"]
 
 
 def finish_affine(records):

@@ -8,7 +8,6 @@
 [Cout, Cin, 3, 3] weight as it is).  Forward, data gradient and weight gradient are three loaders of the same kernel; the
 BatchNorm backward stays the fused `bn_act` kernel.  CPU tensors, a BatchNorm in training mode or other convolution
 shapes take the ATen ops."""
-import ctypes
 import weakref
 
 import torch
@@ -28,8 +27,7 @@ from . import gemm as _gemm_mod
 _WT = {}      # id(weight) -> (version, data_ptr, transposed tensor, event, weak reference: an id can be reused by another tensor)
 
 
-class _WtDesc(ctypes.Structure):              # cim_wt_desc of include/cim_hip.h
-    _fields_ = [("w", ctypes.c_void_p), ("wt", ctypes.c_void_p), ("cin", ctypes.c_int), ("cout", ctypes.c_int)]
+_WtDesc = _lib.STRUCTS["cim_wt_desc"]
 
 
 def _transposed(w):

@@ -23,8 +23,8 @@ from . import gemm as _gemm
 EXACT = os.environ.get("CIM_ROI_FWD_EXACT", "0") == "1"
 
 # kernel forms: CIM_ROI_FWD_* / CIM_ROI_BWD_* of include/cim_hip.h
-FWD_SAMPLE1, FWD_SAMPLE4, FWD_ROWSUM2, FWD_AGG = 0, 1, 2, 3
-BWD_GENERIC1, BWD_GENERIC4, BWD_REGION = 0, 1, 2
+FWD_SAMPLE1, FWD_SAMPLE4, FWD_ROWSUM2, FWD_AGG = (_lib.CONSTANTS["CIM_ROI_FWD_" + k] for k in ("SAMPLE1", "SAMPLE4", "ROWSUM2", "AGG"))
+BWD_GENERIC1, BWD_GENERIC4, BWD_REGION = (_lib.CONSTANTS["CIM_ROI_BWD_" + k] for k in ("GENERIC1", "GENERIC4", "REGION"))
 
 
 def forms(B, C, H, W, K, P, maskcat=False, workspace=True, tables_ready=True):

@@ -23,9 +23,7 @@ import torch
 from .. import _lib
 from .fused import FusedOptimizer
 
-_TENSOR = np.dtype([("p", "<u8"), ("g", "<u8"), ("exp_avg", "<u8"), ("exp_avg_sq", "<u8"), ("n", "<i8"),
-                    ("step_size", "<f4"), ("bc2_sqrt", "<f4"), ("wd", "<f4"), ("rows", "<i4"), ("cols", "<i4"), ("reserved", "<i4"),
-                    ("row_amax", "<u8"), ("col_amax", "<u8")])
+_TENSOR = np.dtype(_lib.STRUCTS["cim_adam_tensor"])
 _REFUSED = ("amsgrad", "maximize", "capturable", "differentiable", "decoupled_weight_decay")
 
 

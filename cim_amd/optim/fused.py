@@ -20,7 +20,7 @@ from ..ops.gemm import join_side as _join_side
 from .. import _lib
 
 CHUNK = 16384          # elements per workgroup
-_CHUNK = np.dtype([("tensor", "<i4"), ("n", "<i4"), ("offset", "<i8")])
+_CHUNK = np.dtype(_lib.STRUCTS["cim_sgd_chunk"])
 MATRIX_MIN = 1 << 20   # weights of at least this many elements are updated in matrix mode (row / column |max| by-product)
 TRAIL_MIN = 1 << 24    # overlap_update: weights of at least this many elements are updated on the side stream (at cfg2: fc1 205 M,
                        # the MaskFuse convolution 18.9 M, fc2 16.8 M elements = 96 % of the update's 5.1 GB of traffic)

@@ -25,8 +25,7 @@ import torch
 from .. import _lib
 from .fused import CHUNK, MATRIX_MIN, TILE_COLS, TILE_ROWS, TRAIL_MIN, FusedOptimizer, _matrix_shape, _Pass  # noqa: F401  (this module's public names)
 
-_TENSOR = np.dtype([("p", "<u8"), ("g", "<u8"), ("buf", "<u8"), ("n", "<i8"), ("lr", "<f4"), ("wd", "<f4"),
-                    ("rows", "<i4"), ("cols", "<i4"), ("row_amax", "<u8"), ("col_amax", "<u8")])
+_TENSOR = np.dtype(_lib.STRUCTS["cim_sgd_tensor"])
 
 
 class SGD(FusedOptimizer):

@@ -13,9 +13,9 @@ import torch
 
 from . import _lib, mask_iou
 
-MAX_POINTS = 256                # CIM_PROP_MAX_POINTS of include/cim_hip.h
-MAX_S = 16                      # CIM_PROP_MAX_S
-MAX_HW = 1 << 22                # CIM_SEGM_MAX_HW
+MAX_POINTS = _lib.CONSTANTS["CIM_PROP_MAX_POINTS"]
+MAX_S = _lib.CONSTANTS["CIM_PROP_MAX_S"]
+MAX_HW = _lib.CONSTANTS["CIM_SEGM_MAX_HW"]
 MAX_SIDE = 65535                # the reference stores boxes as uint16
 
 

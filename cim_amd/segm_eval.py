@@ -14,11 +14,9 @@ import torch
 from . import _lib
 from .utils import rle as _rle
 
-MAX_HW = 1 << 22                # CIM_SEGM_MAX_HW of include/cim_hip.h
-MAX_GT = 1024                   # CIM_SEGM_MAX_GT: ground truths per image
-MAX_DT = 8192                   # CIM_DETECT_MAX_N: detections per (image, category), and maxDets[-1]
-MAX_T, MAX_R, MAX_A, MAX_M = 16, 128, 8, 4
-MAX_POLY_POINTS = 1 << 26       # CIM_POLY_MAX_POINTS: dense points of the polygons of one poly_masks call
+MAX_HW, MAX_GT, MAX_T, MAX_R, MAX_A, MAX_M = (_lib.CONSTANTS["CIM_SEGM_MAX_" + k] for k in ("HW", "GT", "T", "R", "A", "M"))
+MAX_DT = _lib.CONSTANTS["CIM_DETECT_MAX_N"]                 # detections per (image, category), and maxDets[-1]: the detection stage's limit
+MAX_POLY_POINTS = _lib.CONSTANTS["CIM_POLY_MAX_POINTS"]     # dense points of the polygons of one poly_masks call
 MAX_POLY_COORD = float(1 << 20)
 
 AREA_LABELS = ("all", "small", "medium", "large")

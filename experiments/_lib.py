@@ -1,34 +1,13 @@
 """ctypes binding of experiments/libcim_exp.so (experiments/include/cim_exp.h): the superseded engines.  Test infrastructure."""
 import ctypes
 import os
-from ctypes import c_float, c_int, c_longlong, c_void_p
 
-from cim_amd._lib import CimHipError, ptr, stream_ptr      # noqa: F401  (same helpers as the product binding)
+from cim_amd._lib import CimHipError, parse_header, ptr, stream_ptr      # noqa: F401  (same helpers as the product binding)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libcim_exp.so")
-_P = c_void_p
-SIGNATURES = {
-    "cim_gemm_f32_splits": [c_int, c_int, c_int, c_int],
-    "cim_gemm_f32": [_P, _P, _P, _P] + [c_int] * 6 + [c_int, c_int, c_int, c_int, _P, c_int, _P],
-    "cim_conv3x3_f32": [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],
-    "cim_conv3x3_wgrad_f32": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P],
-    "cim_gemm_f32_batched": [_P, _P, _P] + [c_int] * 6 + [c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, c_int, _P],
-    "cim_gemm_f16x2_splits": [c_int, c_int, c_int],
-    "cim_amax_rowcol": [_P, c_int, c_int, c_int, c_int, c_longlong, _P, _P, _P],
-    "cim_gemm_f16x2": [_P, _P, _P, _P] + [c_int] * 6 + [c_int, c_int, c_int, c_int, _P, _P, _P, _P],
-    "cim_gemm_f16x2_batched": [_P, _P, _P] + [c_int] * 6 + [c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, _P, _P, _P],
-    "cim_wino_input_transform": [_P, _P, c_int, c_int, c_int, c_int, _P],
-    "cim_flatten_chw": [_P, _P, _P, c_int, c_int, c_int, c_int, _P],
-    "cim_wino_input_transform_amax": [_P, _P, _P, c_int, c_int, c_int, c_int, _P],
-    "cim_wino_scale_bounds": [_P, _P, c_int, c_int, c_int, c_int, _P],
-    "cim_wino_dy_adjoint_transform": [_P, _P, _P, c_int, c_int, c_int, c_int, _P],
-    "cim_wino_dx_adjoint_output": [_P, _P, c_int, c_int, c_int, c_int, _P],
-    "cim_wino_filter_transform": [_P, _P, c_int, c_int, c_int, c_int, _P],
-    "cim_wino_output_transform": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
-    "cim_wino_dy_transform": [_P, _P, c_int, c_int, c_int, c_int, _P],
-    "cim_wino_wgrad_output": [_P, _P, c_int, c_int, c_int, _P],
-}
+FUNCTIONS = parse_header(os.path.join(HERE, "include", "cim_exp.h"))[0]         # name -> (restype, argtypes)
+SIGNATURES = {name: argtypes for name, (_, argtypes) in FUNCTIONS.items()}
 VALUE_RETURNING = {"cim_gemm_f32_splits", "cim_gemm_f16x2_splits"}
 _lib = None
 
@@ -43,10 +22,9 @@ def load():
         build.build()
     lib = ctypes.CDLL(LIB_PATH)
     lib.cim_last_error.restype = ctypes.c_char_p
-    for name, argtypes in SIGNATURES.items():
+    for name, (restype, argtypes) in FUNCTIONS.items():
         fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = c_int
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
