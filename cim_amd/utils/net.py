@@ -8,6 +8,7 @@ and `optimizer.state[p]['momentum_buffer']`, both of which `cim_amd.optim.SGD` k
 fused HIP update through the per-tensor records `cim_amd.optim.SGD.step` rebuilds every step.
 """
 import logging
+import weakref
 
 import numpy as np
 import torch
@@ -17,15 +18,42 @@ from ..core.config import cfg
 logger = logging.getLogger(__name__)
 
 
-def clip_gradient(model, clip_norm):
-    """Scale all gradients by clip_norm / max(total L2 norm, clip_norm)  (net.py:14-27)."""
-    grads = [p.grad for p in model.parameters() if p.requires_grad and p.grad is not None]
-    if not grads:
-        return
+_CLIPPERS = weakref.WeakKeyDictionary()      # model -> cim_amd.optim.GradClipper over its trainable parameters
+
+
+def _clip_gradient_torch(grads, clip_norm):
+    """The reference's own arithmetic (net.py:14-27), for CPU gradients: one norm per tensor, a host read, one mul_ per tensor."""
     total = torch.sqrt(sum(g.detach().norm() ** 2 for g in grads)).item()
     norm = clip_norm / max(total, clip_norm)
     for g in grads:
         g.mul_(norm)
+
+
+def clip_gradient(model, clip_norm):
+    """Scale all gradients by clip_norm / max(total L2 norm, clip_norm)  (net.py:14-27).
+
+    GPU gradients go through cim_amd.optim.GradClipper (three launches, norm and coefficient stay on the device, no host read);
+    call it after backward() has returned and before optimizer.step().  It cannot be combined with
+    nn.DataParallel.attach_optimizer: the early update has consumed its gradients inside backward, before the global norm exists."""
+    params = [p for p in model.parameters() if p.requires_grad]
+    grads = [p.grad for p in params if p.grad is not None]
+    if not grads:
+        return
+    on_gpu = sum(1 for g in grads if g.is_cuda)
+    if on_gpu == 0:
+        return _clip_gradient_torch(grads, clip_norm)
+    from .. import _lib
+    from ..nn.parallel.data_parallel import DataParallel
+    from ..optim.clip import GradClipper
+    if on_gpu != len(grads):
+        raise _lib.CimHipError("clip_gradient: gradients on the CPU and on a GPU: one device for all of them")
+    if isinstance(model, DataParallel) and model._early is not None:
+        raise _lib.CimHipError("clip_gradient: nn.DataParallel.attach_optimizer is active - the early parameters are already updated "
+                               "inside backward, before the global gradient norm exists; clip without attach_optimizer")
+    clipper = _CLIPPERS.get(model)
+    if clipper is None or len(clipper.params) != len(params) or any(a is not b for a, b in zip(clipper.params, params)):
+        clipper = _CLIPPERS[model] = GradClipper(params)
+    clipper.clip(clip_norm)
 
 
 def _get_lr_change_ratio(cur_lr, new_lr):

@@ -811,6 +811,27 @@ typedef struct cim_adam_tensor {
 int cim_adam_multi(const cim_adam_tensor* tensors, const cim_sgd_chunk* chunks, int n_chunks, double beta1, double beta2, double eps,
                    int max_workgroups, void* stream);
 
+/* Gradient clipping by the global L2 norm (ABI-16 addition: cim_abi_version() stays 16; lib/utils/net.py:15):
+ *     norm = sqrt(sum of g^2 over all gradients) ;  coef = max_norm / max(norm, max_norm) ;  g = g * coef
+ * with the norm and the coefficient kept on the device.  `grads` and `numel` are DEVICE arrays [n_tensors]: the address and
+ * the element count of every (dense, contiguous, fp32) gradient; `chunks` is the fused optimizers' table with flat chunks
+ * only (chunk.tensor indexes grads / numel, offsets are multiples of 4 elements, chunk.n is clamped to the tensor's end).
+ * 16-byte accesses are used for a tensor whose pointer is 16-byte aligned.  max_workgroups: as cim_sgd_multi.
+ * cim_grad_norm_multi: two launches.  The first writes the fp64 sum of squares of every chunk to partial[chunk] (caller's
+ *   workspace, every slot written on every call; no atomics, fixed reduction shape), the second sums them in fp64 in an
+ *   order that only depends on n_chunks and writes out[0] = (float)norm and out[1] = coef:
+ *     NaN when the norm is NaN;  (float)(max_norm / norm), divided in fp64, when norm > max_norm (norm = +inf: 0);  else 1.
+ *   The result is bit-identical for every max_workgroups and from run to run.  max_norm >= 0; +infinity = "norm only".
+ * cim_grad_scale_multi: one launch behind it on the same stream.  Every workgroup reads out[1]; when it is exactly 1.0f it
+ *   returns without touching a gradient, otherwise g = g * out[1] in place (a NaN coefficient makes every gradient NaN).
+ * n_chunks == 0: nothing is launched and `out` is left untouched.  No element at or beyond a tensor's end is read or written. */
+int cim_grad_norm_multi(const uint64_t* grads, const int64_t* numel, int n_tensors,
+                        const cim_sgd_chunk* chunks, int n_chunks, double* partial /* [n_chunks] */,
+                        double max_norm, float* out /* [2]: norm, coef */, int max_workgroups, void* stream);
+int cim_grad_scale_multi(const uint64_t* grads, const int64_t* numel, int n_tensors,
+                         const cim_sgd_chunk* chunks, int n_chunks, const float* out,
+                         int max_workgroups, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
