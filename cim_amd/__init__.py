@@ -25,6 +25,9 @@ ALIASES = {
     "datasets.voc_eval": "cim_amd.datasets.voc_eval",                  # lib/datasets/voc_eval.py
     "datasets.dis_eval": "cim_amd.datasets.dis_eval",                  # lib/datasets/dis_eval.py
 }
+# routed only on request, install_as_lib(route_training_stats=True): lib/utils/training_stats.py as tools/train.py:31 imports it
+TRAINING_STATS = {"utils.training_stats": "cim_amd.utils.training_stats"}
+_routed = dict(ALIASES)            # what the finder resolves right now
 
 
 class _AliasLoader(importlib.abc.Loader):
@@ -55,7 +58,7 @@ class _CfgBindingLoader(importlib.abc.Loader):
 
 class _Finder(importlib.abc.MetaPathFinder):
     def find_spec(self, fullname, path=None, target=None):
-        real = ALIASES.get(fullname)
+        real = _routed.get(fullname)
         if real is not None:
             is_pkg = fullname in ("ops", "nn.parallel")
             return importlib.machinery.ModuleSpec(fullname, _AliasLoader(real), is_package=is_pkg)
@@ -70,14 +73,18 @@ class _Finder(importlib.abc.MetaPathFinder):
 _finder = _Finder()
 
 
-def install_as_lib():
+def install_as_lib(route_training_stats=False):
     """Call once before the reference's `lib/` modules are imported (e.g. first line of tools/train.py).
-    Idempotent.  Modules of `ALIASES` that the process already imported from the reference tree are replaced."""
+    Idempotent.  Modules of `ALIASES` that the process already imported from the reference tree are replaced.
+    route_training_stats=True also resolves `utils.training_stats` to cim_amd.utils.training_stats, until
+    `uninstall_as_lib()`; the default leaves the reference's own module in place."""
+    if route_training_stats:
+        _routed.update(TRAINING_STATS)
     if _finder not in sys.meta_path:
         sys.meta_path.insert(0, _finder)
-    for name in ALIASES:
+    for name, real in _routed.items():
         mod = sys.modules.get(name)
-        if mod is not None and mod.__name__ != ALIASES[name]:
+        if mod is not None and mod.__name__ != real:
             del sys.modules[name]
     ref_cfg = sys.modules.get("core.config")
     if ref_cfg is not None and hasattr(ref_cfg, "cfg"):
@@ -89,9 +96,11 @@ def uninstall_as_lib():
     """Undo `install_as_lib()` (tests)."""
     if _finder in sys.meta_path:
         sys.meta_path.remove(_finder)
-    for name, real in ALIASES.items():
+    for name, real in _routed.items():
         mod = sys.modules.get(name)
         if mod is not None and mod.__name__ == real:
             del sys.modules[name]
+    for name in TRAINING_STATS:
+        _routed.pop(name, None)
     from .core import config as own
     own.reset_cfg()

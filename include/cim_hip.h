@@ -832,6 +832,37 @@ int cim_grad_scale_multi(const uint64_t* grads, const int64_t* numel, int n_tens
                          const cim_sgd_chunk* chunks, int n_chunks, const float* out,
                          int max_workgroups, void* stream);
 
+/* ------------------------------------------------------------------ training statistics (ABI-16 addition)
+ * The bookkeeping of TrainingStats.UpdateIterStats / GetStats (lib/utils/training_stats.py:65-128,149-167) and of its
+ * SmoothedValue (lib/utils/logging.py:60-85) on the device: csrc/train_stats.hip, DESIGN.md 4.17.  Additive:
+ * cim_abi_version() stays 16.  `state` is the caller's device buffer of cim_stats_bytes(n_keys, window) bytes, 8-byte
+ * aligned, ZERO-FILLED ONCE before the first call, one per tracker; n_keys (tracked scalars per push, the total not
+ * counted) and window must be the same in every call on one state.  Calls on different states are independent.
+ *
+ * cim_stats_push: one single-wave launch.  `values_host` is a HOST array of n_values device addresses of fp32 scalars v_0 ..,
+ * read before the call returns: the addresses travel in the kernel arguments (autograd hands out new loss tensors every
+ * step; there is no device table to refresh).  All arithmetic is fp32, every operation rounded on its own:
+ *   t = ((0 + v_0) + v_1) + ... over the first n_sum values, in argument order (training_stats.py:72-77); the remaining
+ *   values (a gradient norm, ...) are tracked and are not part of t.  Columns: the n_values values, then t.
+ *   iter_size == 1: every column commits its value.  Otherwise acc = (inner == 0 ? 0 : acc) + x per column, and the call
+ *   with inner == iter_size - 1 commits acc / (float)iter_size, IEEE division (:106-128; the total's statistic is the mean
+ *   of the per-inner totals).
+ *   A commit writes slot (count % window) of the ring [window][n_values + 1], adds to a per-column fp64 running sum,
+ *   increments count and, if any committed value is not finite and none was before, records the 1-based commit number.
+ * cim_stats_summary: one single-wave launch.  out: float [n_keys + 1][3] = per column (median, last committed value, global
+ *   mean = fp64 sum / count rounded to fp32), then int32 [2] = (first non-finite commit or 0, count): 3 (n_keys + 1) + 2
+ *   4-byte words.  The median is np.median's over the n = min(count, window) committed values: ascending sort, the middle
+ *   element for odd n, (a + b) / 2 in fp32 for even n, NaN when the window holds a NaN or n == 0 (then last and mean are NaN too).
+ * Refused before any launch (-1, cim_last_error() names the condition; the state is untouched): n_values / n_keys outside
+ * 1..CIM_STATS_MAX_KEYS, n_sum > n_values, window outside 1..CIM_STATS_MAX_WIN, iter_size < 1, inner outside [0, iter_size),
+ * a null or misaligned address.  Nothing outside the state's cim_stats_bytes and out's words is read or written. */
+#define CIM_STATS_MAX_KEYS 16
+#define CIM_STATS_MAX_WIN 64
+long long cim_stats_bytes(int n_keys, int window);
+int cim_stats_push(const uint64_t* values_host, int n_values, int n_sum, int window, int iter_size, int inner, void* state,
+                   void* stream);
+int cim_stats_summary(void* state, int n_keys, int window, float* out /* [3 (n_keys + 1) + 2] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
