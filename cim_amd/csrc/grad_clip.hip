@@ -64,10 +64,10 @@ __global__ __launch_bounds__(256) void grad_sqsum_kernel(const uint64_t* __restr
     double a[4] = {0.0, 0.0, 0.0, 0.0};
     int i = threadIdx.x * 4;
     for (; i + 3 * 1024 < n4; i += 4 * 1024) {           // 4 x 16 B loads in flight per lane
-        const float4 v0 = sgd_load(g + i), v1 = sgd_load(g + i + 1024), v2 = sgd_load(g + i + 2048), v3 = sgd_load(g + i + 3072);
+        const float4 v0 = stream_load(g + i), v1 = stream_load(g + i + 1024), v2 = stream_load(g + i + 2048), v3 = stream_load(g + i + 3072);
         sq4(a, v0); sq4(a, v1); sq4(a, v2); sq4(a, v3);
     }
-    for (; i < n4; i += 1024) sq4(a, sgd_load(g + i));
+    for (; i < n4; i += 1024) sq4(a, stream_load(g + i));
     for (int j = n4 + threadIdx.x; j < n; j += 256)     // unaligned tensors / tails
         a[0] = fma((double)g[j], (double)g[j], a[0]);
     const double s = block_sum((a[0] + a[1]) + (a[2] + a[3]), lds);
@@ -104,17 +104,13 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(const uint64_t* __restr
     for (; i + 3 * 1024 < n4; i += 4 * 1024) {           // 4 x 16 B loads in flight per lane, as in the norm launch
         float4 v[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = sgd_load(g + i + k * 1024);
+        for (int k = 0; k < 4; ++k) v[k] = stream_load(g + i + k * 1024);
 #pragma unroll
         for (int k = 0; k < 4; ++k) *reinterpret_cast<float4*>(g + i + k * 1024) = scale4(v[k], coef);
     }
-    for (; i < n4; i += 1024) *reinterpret_cast<float4*>(g + i) = scale4(sgd_load(g + i), coef);
+    for (; i < n4; i += 1024) *reinterpret_cast<float4*>(g + i) = scale4(stream_load(g + i), coef);
     for (int j = n4 + threadIdx.x; j < n; j += 256) g[j] *= coef;
   }
-}
-
-inline int grid_of(int n_chunks, int max_workgroups) {
-    return max_workgroups > 0 && max_workgroups < n_chunks ? max_workgroups : n_chunks;
 }
 
 }  // namespace
@@ -126,7 +122,7 @@ extern "C" int cim_grad_norm_multi(const uint64_t* grads, const int64_t* numel, 
     if (n_chunks == 0) return 0;
     CIM_CHECK_ARG(grads != nullptr && numel != nullptr && chunks != nullptr && partial != nullptr && out != nullptr);
     CIM_CHECK_ARG(n_tensors > 0);
-    hipLaunchKernelGGL(grad_sqsum_kernel, dim3(grid_of(n_chunks, max_workgroups)), dim3(256), 0, cim::as_stream(stream), grads, numel,
+    hipLaunchKernelGGL(grad_sqsum_kernel, dim3(optim_grid(n_chunks, max_workgroups)), dim3(256), 0, cim::as_stream(stream), grads, numel,
                        n_tensors, chunks, n_chunks, partial);
     CIM_CHECK_LAUNCH();
     hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, cim::as_stream(stream), partial, n_chunks, max_norm, out);
@@ -140,7 +136,7 @@ extern "C" int cim_grad_scale_multi(const uint64_t* grads, const int64_t* numel,
     if (n_chunks == 0) return 0;
     CIM_CHECK_ARG(grads != nullptr && numel != nullptr && chunks != nullptr && out != nullptr);
     CIM_CHECK_ARG(n_tensors > 0);
-    hipLaunchKernelGGL(grad_scale_kernel, dim3(grid_of(n_chunks, max_workgroups)), dim3(256), 0, cim::as_stream(stream), grads, numel,
+    hipLaunchKernelGGL(grad_scale_kernel, dim3(optim_grid(n_chunks, max_workgroups)), dim3(256), 0, cim::as_stream(stream), grads, numel,
                        n_tensors, chunks, n_chunks, out);
     CIM_CHECK_LAUNCH();
     return 0;

@@ -15,22 +15,14 @@ import torch
 
 from .. import _lib
 from ..ops.gemm import join_side as _join_side
-from .fused import _CHUNK, CHUNK
+from . import fused
 
 _NAME = "cim_amd.optim.GradClipper"
 
 
 def chunk_table(sizes):
-    """Flat chunks (cim_sgd_chunk records) of tensors with `sizes` elements: CHUNK elements each, the last one of a tensor clamped
-    to its end."""
-    parts = []
-    for ti, n in enumerate(sizes):
-        cnt = (n + CHUNK - 1) // CHUNK
-        tab = np.empty(cnt, dtype=_CHUNK)
-        tab["tensor"], tab["offset"] = ti, np.arange(cnt, dtype=np.int64) * CHUNK
-        tab["n"] = np.minimum(CHUNK, n - tab["offset"])
-        parts.append(tab)
-    return np.concatenate(parts) if parts else np.empty(0, dtype=_CHUNK)
+    """fused.chunk_table for flat tensors of `sizes` elements."""
+    return fused.chunk_table([(n, 0, 0) for n in sizes])
 
 
 class GradClipper:
@@ -64,11 +56,9 @@ class GradClipper:
         self._t = dict(
             n_chunks=int(chunks.shape[0]), chunks=torch.from_numpy(chunks.view(np.uint8).reshape(-1).copy()).to(dev),
             tab=np.zeros(2 * n, dtype=np.uint64),       # addresses [n], then element counts [n] (int64 on the device)
-            pinned=torch.empty(16 * n, dtype=torch.uint8).pin_memory(), table=torch.empty(16 * n, dtype=torch.uint8, device=dev),
-            partial=torch.empty(chunks.shape[0], dtype=torch.float64, device=dev), out=torch.empty(2, dtype=torch.float32, device=dev),
-            copied=None, sig=None)
+            staged=fused.StagedTable(16 * n, dev),
+            partial=torch.empty(chunks.shape[0], dtype=torch.float64, device=dev), out=torch.empty(2, dtype=torch.float32, device=dev))
         self._t["tab"][n:] = sizes
-        self._t["staging"] = self._t["pinned"].numpy()      # (the pinned buffer as the host sees it)
         self._layout = layout
 
     @torch.no_grad()
@@ -83,16 +73,7 @@ class GradClipper:
         t, n = self._t, len(grads)
         t["tab"][:n] = [g.data_ptr() for g in grads]
         with torch.cuda.device(dev):
-            sig = t["tab"].tobytes()
-            if sig != t["sig"]:
-                if t["copied"] is not None:
-                    t["copied"].synchronize()           # the previous H2D copy out of the staging buffer (long done in practice)
-                t["staging"][:] = t["tab"].view(np.uint8)
-                t["table"].copy_(t["pinned"], non_blocking=True)
-                t["copied"] = torch.cuda.Event()
-                t["copied"].record()
-                t["sig"] = sig
-            base, stream = t["table"].data_ptr(), _lib.stream_ptr()
+            base, stream = t["staged"].upload(t["tab"]), _lib.stream_ptr()
             args = (base, base + 8 * n, n, t["chunks"].data_ptr(), t["n_chunks"])
             _lib.call("cim_grad_norm_multi", *args, t["partial"].data_ptr(), float(max_norm), t["out"].data_ptr(), 0, stream)
             if scale:

@@ -15,9 +15,8 @@ waits of `wait_update`, `state_dict` and `zero_grad(set_to_none=False)`.
 import numpy as np
 import torch
 
-from ..ops.gemm import join_side as _join_side
-
 from .. import _lib
+from ..ops.gemm import join_side as _join_side
 
 CHUNK = 16384          # elements per workgroup
 _CHUNK = np.dtype(_lib.STRUCTS["cim_sgd_chunk"])
@@ -34,6 +33,49 @@ def _matrix_shape(p):
     rows = p.shape[0]
     cols = p.numel() // rows
     return (rows, cols) if cols % 4 == 0 else None
+
+
+def chunk_table(layout):
+    """The chunk table (cim_sgd_chunk records) of tensors with `layout` = (numel, rows, cols) each, rows = cols = 0 for a flat
+    tensor: CHUNK elements per flat chunk, the last one of a tensor clamped to its end (the kernels take min(n, elements left)
+    themselves, so clamped and unclamped n are the same update); 64 x 1024 tiles of a matrix-mode tensor, offset = first row,
+    n = first column."""
+    parts = []
+    for ti, (n, rows, cols) in enumerate(layout):
+        if cols > 0:
+            r0, c0 = np.meshgrid(np.arange(0, rows, TILE_ROWS), np.arange(0, cols, TILE_COLS), indexing="ij")
+            tab = np.empty(r0.size, dtype=_CHUNK)
+            tab["offset"], tab["n"] = r0.reshape(-1), c0.reshape(-1)
+        else:
+            tab = np.empty((n + CHUNK - 1) // CHUNK, dtype=_CHUNK)
+            tab["offset"] = np.arange(len(tab), dtype=np.int64) * CHUNK
+            tab["n"] = np.minimum(CHUNK, n - tab["offset"])
+        tab["tensor"] = ti
+        parts.append(tab)
+    return np.concatenate(parts) if parts else np.empty(0, dtype=_CHUNK)
+
+
+class StagedTable:
+    """A per-step host table on the device: staged in pinned memory and copied (on the current stream) only when its bytes
+    differ from the previous upload's.  upload() returns the device address."""
+
+    def __init__(self, nbytes, dev):
+        self.pinned = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        self.table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self._host = self.pinned.numpy()                 # the pinned buffer as the host sees it
+        self._sig = self._copied = None
+
+    def upload(self, tab):
+        sig = tab.tobytes()
+        if sig != self._sig:
+            if self._copied is not None:
+                self._copied.synchronize()               # the previous H2D copy out of the staging buffer (long done in practice)
+            self._host[:] = np.frombuffer(sig, dtype=np.uint8)
+            self.table.copy_(self.pinned, non_blocking=True)
+            self._copied = torch.cuda.Event()
+            self._copied.record()
+            self._sig = sig
+        return self.table.data_ptr()
 
 
 class _Pass:
@@ -86,24 +128,6 @@ class FusedOptimizer(torch.optim.Optimizer):
         raise NotImplementedError
 
     # ------------------------------------------------------------------ tables
-    def _build_chunks(self, ps, layout, dev):
-        """layout: per tensor (numel, rows, cols) with rows = cols = 0 for flat tensors."""
-        parts = []
-        for ti, (n, rows, cols) in enumerate(layout):
-            if cols > 0:        # matrix mode: 64 x 1024 tiles, offset = first row, n = first column
-                r0, c0 = np.meshgrid(np.arange(0, rows, TILE_ROWS), np.arange(0, cols, TILE_COLS), indexing="ij")
-                tab = np.empty(r0.size, dtype=_CHUNK)
-                tab["offset"], tab["n"] = r0.reshape(-1), c0.reshape(-1)
-            else:
-                cnt = (n + CHUNK - 1) // CHUNK
-                tab = np.empty(cnt, dtype=_CHUNK)
-                tab["offset"], tab["n"] = np.arange(cnt, dtype=np.int64) * CHUNK, CHUNK
-            tab["tensor"] = ti
-            parts.append(tab)
-        tab = np.concatenate(parts)
-        ps.chunks = torch.from_numpy(tab.view(np.uint8).reshape(-1).copy()).to(dev)
-        ps.n_chunks, ps.layout = int(tab.shape[0]), tuple(layout)
-
     def _scan(self, ps, select):
         """Slow path (first step, or when the set of parameters with gradients changed): validate every selected tensor and
         cache what does not change from step to step - parameter and state pointers, sizes, matrix shapes, the device
@@ -144,14 +168,15 @@ class FusedOptimizer(torch.optim.Optimizer):
                 off += ms[0] + ms[1]
         layout = tuple((int(tab["n"][i]), int(tab["rows"][i]), int(tab["cols"][i])) for i in range(n))
         if layout != ps.layout or ps.chunks is None or ps.chunks.device != dev:
-            self._build_chunks(ps, layout, dev)
+            chunks = chunk_table(layout)
+            ps.chunks, ps.n_chunks, ps.layout = torch.from_numpy(chunks.view(np.uint8).reshape(-1).copy()).to(dev), len(chunks), layout
         touched = []
         for p, state, _ in recs:
             touched += [p, *state]
+        staged = StagedTable(tab.nbytes, dev)
         ps.cache = dict(recs=recs, tab=tab, amax_off=amax_off, n_amax=off, rule=rule, dev=dev, touched=touched,
-                        pinned=torch.empty(tab.nbytes, dtype=torch.uint8).pin_memory(),
-                        table=torch.empty(tab.nbytes, dtype=torch.uint8, device=dev), copied=None,
-                        group_of=np.array([gi for _, _, gi in recs]), sig=None, ids=frozenset(id(p) for p, _, _ in recs))
+                        staged=staged, table=staged.table,       # `table`: the records on the device, what _launch passes
+                        group_of=np.array([gi for _, _, gi in recs]), ids=frozenset(id(p) for p, _, _ in recs))
         return True
 
     def _pointers_moved(self, c):
@@ -214,16 +239,7 @@ class FusedOptimizer(torch.optim.Optimizer):
         for i, off, rows, cols in c["amax_off"]:
             tab["row_amax"][i], tab["col_amax"][i] = base + 4 * off, base + 4 * (off + rows)
             slices.append((c["recs"][i][0], amax_buf[off:off + rows], amax_buf[off + rows:off + rows + cols], rows, cols))
-        raw = tab.view(np.uint8).reshape(-1)
-        sig = raw.tobytes()
-        if sig != c["sig"]:
-            if c["copied"] is not None:
-                c["copied"].synchronize()               # the previous H2D copy out of the staging buffer (long done in practice)
-            c["pinned"].numpy()[:] = raw
-            c["table"].copy_(c["pinned"], non_blocking=True)
-            c["copied"] = torch.cuda.Event()
-            c["copied"].record()
-            c["sig"] = sig
+        c["staged"].upload(tab)
         self._launch(c, ps, self.trail_workgroups if key == "trail" else 0)
         # the kernel wrote parameters and state tensors through raw pointers: tell autograd's version counters, so that
         # anything keyed by Tensor._version (saved-tensor checks, caches) sees the in-place update
