@@ -185,6 +185,29 @@ def _post_check(c):
             raise NotImplementedError("TEST.%s.ENABLED (no shipped config enables it)" % k)
 
 
+_SOFT_NMS_DEFAULTS = dict(ENABLED=False, METHOD="linear", SIGMA=0.5)                          # lib/core/config.py:206-212
+_BBOX_VOTE_DEFAULTS = dict(ENABLED=False, VOTE_TH=0.8, SCORING_METHOD="ID")                   # :218-229
+
+
+def _soft_vote_cfg(c):
+    """TEST.SOFT_NMS / TEST.BBOX_VOTE of cfg `c` as cim_amd.detect.postprocess's (soft_nms, box_vote); None where off.
+    The reference's call fixes the soft-NMS minimum score at 0.0001 and leaves box_voting's beta at 1.0 (test.py:379-396)."""
+    t = c.TEST if "TEST" in c else {}
+
+    def get(group, defaults, key):
+        g = t[group] if group in t else {}
+        return g[key] if key in g else defaults[key]
+
+    soft = vote = None
+    if get("SOFT_NMS", _SOFT_NMS_DEFAULTS, "ENABLED"):
+        soft = dict(method=get("SOFT_NMS", _SOFT_NMS_DEFAULTS, "METHOD"), sigma=get("SOFT_NMS", _SOFT_NMS_DEFAULTS, "SIGMA"),
+                    min_score=0.0001)
+    if get("BBOX_VOTE", _BBOX_VOTE_DEFAULTS, "ENABLED"):
+        vote = dict(thresh=get("BBOX_VOTE", _BBOX_VOTE_DEFAULTS, "VOTE_TH"),
+                    scoring_method=get("BBOX_VOTE", _BBOX_VOTE_DEFAULTS, "SCORING_METHOD"), beta=1.0)
+    return soft, vote
+
+
 def _nms_limit_records(c, scores, boxes, max_det):
     """The reference's per-class threshold + NMS + limit of cfg `c`, on the device: host (idx, cls, score, count, boxes)."""
     _post_check(c)
@@ -217,9 +240,21 @@ def _dets(boxes_h, idx, score):
 def box_results_with_nms_and_limit(scores, boxes):
     """test.py:355-420: (scores, boxes, cls_boxes) with cls_boxes of length NUM_CLASSES + 1, cls_boxes[0] == [] and
     float32 [k, 5] arrays (x1, y1, x2, y2, score) in ascending proposal order.  scores [N, C] f32 and boxes [N, 4]: device
-    tensors (im_detect_all's) or NumPy arrays."""
-    idx, cls, sc, count, boxes_h = _nms_limit_records(cfg, scores, boxes, _post_cfg(cfg, "DETECTIONS_PER_IM"))
-    cls_boxes = _shift(_per_class(_dets(boxes_h, idx, sc), count))
+    tensors (im_detect_all's) or NumPy arrays.  TEST.SOFT_NMS.ENABLED: rows in selection order with the decayed scores;
+    TEST.BBOX_VOTE.ENABLED: voted boxes and, by SCORING_METHOD, scores; the limit comes after both (test.py:378-408)."""
+    soft, vote = _soft_vote_cfg(cfg)
+    if soft is None and vote is None:
+        idx, cls, sc, count, boxes_h = _nms_limit_records(cfg, scores, boxes, _post_cfg(cfg, "DETECTIONS_PER_IM"))
+        rows = _dets(boxes_h, idx, sc)
+    else:
+        # test.py:378-396: rows in selection order with the decayed scores under soft-NMS, voted boxes / scores under voting
+        s, b, _ = detect.device_inputs(scores, boxes)
+        det = detect.postprocess(s, b, _post_cfg(cfg, "SCORE_THRESH"), _post_cfg(cfg, "NMS"),
+                                 _post_cfg(cfg, "DETECTIONS_PER_IM"), soft_nms=soft, box_vote=vote,
+                                 num_classes=cfg.MODEL.NUM_CLASSES)
+        _, _, sc, count, bx = detect.softvote_to_host(det)
+        rows = np.hstack((bx, sc[:, None])).astype(np.float32, copy=False)
+    cls_boxes = _shift(_per_class(rows, count))
     out_scores, out_boxes = _flat(cls_boxes, cfg.MODEL.NUM_CLASSES)
     return out_scores, out_boxes, cls_boxes
 

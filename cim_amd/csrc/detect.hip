@@ -23,10 +23,13 @@
 // 1-D grid (a binary search finds a tile's image), the NMS on a (C, B) grid, one limit workgroup per image, and the
 // compaction of the per-image records into one array.  Each per-image body below (overlap_tile, nms_class, limit_image) is
 // ONE __device__ function called by both forms with base pointers, so the exactness contract holds for both.
+// Soft-NMS and box voting (TEST.SOFT_NMS / TEST.BBOX_VOTE) are at the end of the file; they share the overlap
+// helpers, the block scan and the limit's radix select with the kernels above.
 #pragma clang fp contract(off)                      // (x2 - x1 + 1) * ... and iarea + area - w*h: no fused multiply-adds
 #include "common.h"
 #include "../../include/cim_hip.h"
 #include <limits.h>
+#include <algorithm>
 
 namespace {
 
@@ -217,41 +220,12 @@ __global__ __launch_bounds__(1024) void detect_nms_kernel(const float* __restric
     nms_class(scores, ld, boxes, N, W, score_thr, nms_thr, mat, keepbits + (size_t)c * W, c, nullptr, s_key);
 }
 
-// test.py:395-403: the kept set in (class, proposal) order, thresholded at the max_det-th largest kept score when more
-// than max_det are kept.  det records: (proposal, class, score bits).  cmask [C] (null: every class): classes whose
-// records are written - applied AFTER the limit (generate_mask_for_MaskRCNN.py:124-136 limits over all classes first)
-__device__ __forceinline__ void limit_image(const float* __restrict__ scores, int ld, int C, int W, int max_det,
-                                            const unsigned long long* __restrict__ keepbits, uint32_t* __restrict__ lkey,
-                                            int* __restrict__ lidx, int* __restrict__ lcls, int* __restrict__ det,
-                                            int* __restrict__ count, int* __restrict__ total,
-                                            const unsigned char* __restrict__ cmask) {
-    __shared__ int s_part[16];
+// np.sort(image_scores)[-max_det] over the T orderable keys of lkey: the max_det-th largest, four 8-bit digits from the top.
+// 0 (below every candidate key) when no limit applies.  The whole 1024-lane workgroup calls it, lkey visible to all lanes.
+__device__ __forceinline__ uint32_t limit_threshold(const uint32_t* __restrict__ lkey, int T, int max_det) {
     __shared__ unsigned s_hist[256];
     __shared__ unsigned s_prefix, s_k;
     const int tid = threadIdx.x;
-    for (int c = tid; c < C; c += 1024) count[c] = 0;
-    __threadfence();                                                   // (the zeros reach L2 before any atomic below)
-    // compaction of the kept bits: word (c, w) of keepbits is the flat word c * W + w, so flat order = output order
-    const int nw = C * W;
-    int T = 0;
-    for (int base = 0; base < nw; base += 1024) {
-        const int qw = base + tid;
-        unsigned long long word = qw < nw ? keepbits[qw] : 0ull;
-        int tot;
-        int o = T + block_exclusive_scan((int)__popcll(word), s_part, &tot);
-        const int c = qw / W, p0 = (qw - c * W) * 64;
-        while (word) {
-            const int p = p0 + __builtin_ctzll(word);
-            word &= word - 1;
-            lkey[o] = orderable(scores[(size_t)p * ld + c]);
-            lidx[o] = p;
-            lcls[o] = c;
-            ++o;
-        }
-        T += tot;
-    }
-    __syncthreads();
-    // np.sort(image_scores)[-max_det]: the max_det-th largest, four 8-bit digits from the top
     uint32_t thr_key = 0;                                              // (every candidate key is > 0)
     if (max_det > 0 && T > max_det) {
         uint32_t prefix = 0, mask = 0;
@@ -282,6 +256,42 @@ __device__ __forceinline__ void limit_image(const float* __restrict__ scores, in
         }
         thr_key = prefix;
     }
+    return thr_key;
+}
+
+// test.py:395-403: the kept set in (class, proposal) order, thresholded at the max_det-th largest kept score when more
+// than max_det are kept.  det records: (proposal, class, score bits).  cmask [C] (null: every class): classes whose
+// records are written - applied AFTER the limit (generate_mask_for_MaskRCNN.py:124-136 limits over all classes first)
+__device__ __forceinline__ void limit_image(const float* __restrict__ scores, int ld, int C, int W, int max_det,
+                                            const unsigned long long* __restrict__ keepbits, uint32_t* __restrict__ lkey,
+                                            int* __restrict__ lidx, int* __restrict__ lcls, int* __restrict__ det,
+                                            int* __restrict__ count, int* __restrict__ total,
+                                            const unsigned char* __restrict__ cmask) {
+    __shared__ int s_part[16];
+    const int tid = threadIdx.x;
+    for (int c = tid; c < C; c += 1024) count[c] = 0;
+    __threadfence();                                                   // (the zeros reach L2 before any atomic below)
+    // compaction of the kept bits: word (c, w) of keepbits is the flat word c * W + w, so flat order = output order
+    const int nw = C * W;
+    int T = 0;
+    for (int base = 0; base < nw; base += 1024) {
+        const int qw = base + tid;
+        unsigned long long word = qw < nw ? keepbits[qw] : 0ull;
+        int tot;
+        int o = T + block_exclusive_scan((int)__popcll(word), s_part, &tot);
+        const int c = qw / W, p0 = (qw - c * W) * 64;
+        while (word) {
+            const int p = p0 + __builtin_ctzll(word);
+            word &= word - 1;
+            lkey[o] = orderable(scores[(size_t)p * ld + c]);
+            lidx[o] = p;
+            lcls[o] = c;
+            ++o;
+        }
+        T += tot;
+    }
+    __syncthreads();
+    const uint32_t thr_key = limit_threshold(lkey, T, max_det);
     // keep score >= image_thresh (ties at the threshold all stay, as in the reference)
     int outn = 0;
     for (int base = 0; base < T; base += 1024) {
@@ -682,6 +692,438 @@ extern "C" int cim_detect_corloc(const float* scores, int ld, int N, int C, int*
     CIM_CHECK_ARG(ld >= C);
     CIM_CHECK_ARG(scores && out);
     hipLaunchKernelGGL(detect_corloc_kernel, dim3(C), dim3(256), 0, cim::as_stream(stream), scores, ld, N, out);
+    CIM_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---------------------------------------------------------------- soft-NMS, box voting and their limit
+// TEST.SOFT_NMS / TEST.BBOX_VOTE of box_results_with_nms_and_limit (lib/core/test.py:378-396): cython_nms.pyx:98-203,
+// boxes.py:268-317 over cython_bbox.pyx:32-73.  Per class the records (proposal, class, score bits) go to srec[c][.] in the
+// reference's order - selection order under soft-NMS, ascending proposal after the greedy pass -, the voting kernel rewrites
+// their scores and fills vbox, and one limit workgroup writes the records that reach the limit, their order preserved.
+namespace {
+
+// cython_nms.pyx:166-172 and cython_bbox.pyx:52-72 are the same fp32 expression: t the selected / top box, b the examined
+// one.  false (no overlap computed: the pyx skips the row, bbox_overlaps leaves 0) unless iw > 0 and ih > 0.
+__device__ __forceinline__ bool guarded_overlap(float4 t, float4 b, float* ov) {
+    const float area = (b.z - b.x + 1.0f) * (b.w - b.y + 1.0f);
+    const float iw = pyx_min(t.z, b.z) - pyx_max(t.x, b.x) + 1.0f;
+    if (!(iw > 0.0f)) return false;
+    const float ih = pyx_min(t.w, b.w) - pyx_max(t.y, b.y) + 1.0f;
+    if (!(ih > 0.0f)) return false;
+    const float ua = (t.z - t.x + 1.0f) * (t.w - t.y + 1.0f) + area - iw * ih;
+    *ov = iw * ih / ua;                                                 // correctly rounded fp32 division
+    return true;
+}
+
+// cython_nms.pyx:174-187: the decayed score weight * s
+__device__ __forceinline__ float soft_decay(int kind, float ov, float nt, float sigma, float s) {
+    float weight;
+    if (kind == CIM_SOFTVOTE_NMS_SOFT_LINEAR) weight = ov > nt ? 1.0f - ov : 1.0f;
+    else if (kind == CIM_SOFTVOTE_NMS_SOFT_GAUSSIAN) weight = (float)exp((double)(-(ov * ov) / sigma));   // np.exp: double
+    else weight = ov > nt ? 0.0f : 1.0f;
+    return weight * s;
+}
+
+// the scan of cython_nms.pyx:128-132 keeps the FIRST position of the maximum (strict <)
+struct SoftBest {
+    float s;
+    int q;
+};
+__device__ __forceinline__ SoftBest soft_better(SoftBest a, SoftBest b) {
+    return (b.s > a.s || (b.s == a.s && b.q < a.q)) ? b : a;
+}
+
+// One workgroup per class.  LDS: perm [N] i32 (position -> proposal), score [N] f32, hole [N / 2 + 1] u16.
+// Per selection step i: argmax over [i, n) and its swap to i; every later position is examined once against the selected
+// box (decay + survival flag); then the pyx's swap-with-last removal as a partition: with M survivors the holes (removed
+// positions below i + 1 + M, ascending) take the survivors at positions >= i + 1 + M in descending order.
+__global__ __launch_bounds__(1024) void softvote_soft_nms_kernel(const float* __restrict__ scores, int ld,
+                                                                 const float4* __restrict__ boxes, int N, float score_thr,
+                                                                 float nt, float sigma, float min_score, int kind,
+                                                                 int* __restrict__ srec, int* __restrict__ scnt) {
+    extern __shared__ int s_dyn[];
+    __shared__ int s_part[16];
+    __shared__ SoftBest s_best[16];
+    __shared__ int s_wcnt[128];
+    int* s_perm = s_dyn;
+    float* s_sc = reinterpret_cast<float*>(s_dyn + N);
+    unsigned short* s_hole = reinterpret_cast<unsigned short*>(s_dyn + 2 * (size_t)N);
+    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long below = (1ull << lane) - 1;
+    // dets_j: the candidates s > float32(SCORE_THRESH) in ascending proposal order
+    int n = 0;
+    for (int base = 0; base < N; base += 1024) {
+        const int p = base + tid;
+        const float s = p < N ? scores[(size_t)p * ld + c] : 0.0f;
+        const bool cand = p < N && s > score_thr;
+        int tot;
+        const int o = n + block_exclusive_scan(cand ? 1 : 0, s_part, &tot);
+        if (cand) {
+            s_perm[o] = p;
+            s_sc[o] = s;
+        }
+        n += tot;
+    }
+    __syncthreads();
+    int* rec = srec + 3 * (size_t)c * N;
+    for (int i = 0; i < n; ++i) {                                       // (n is uniform over the workgroup)
+        SoftBest b = {-INFINITY, INT_MAX};
+        for (int q = i + tid; q < n; q += 1024) b = soft_better(b, SoftBest{s_sc[q], q});
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) b = soft_better(b, SoftBest{__shfl_xor(b.s, o), __shfl_xor(b.q, o)});
+        if (lane == 0) s_best[wave] = b;
+        __syncthreads();
+        b = s_best[0];
+#pragma unroll
+        for (int w = 1; w < 16; ++w) b = soft_better(b, s_best[w]);
+        const int m = b.q;                                              // i <= m < n
+        const int pm = s_perm[m], pi = s_perm[i];
+        const float sm = s_sc[m], si = s_sc[i];
+        __syncthreads();                                                // (rows i and m and s_best have been read)
+        // the swap: lane 0 writes row i and the record, the lane that examines position m writes row m below
+        if (tid == 0) {
+            s_perm[i] = pm;
+            s_sc[i] = sm;
+            rec[3 * i] = pm;
+            rec[3 * i + 1] = c;
+            rec[3 * i + 2] = __float_as_int(sm);
+        }
+        const float4 t = boxes[pm];
+        const int lo = i + 1;
+        const int tiles = (n - lo + 1023) >> 10;                        // <= 8: N <= 8192
+        unsigned long long bal[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            bal[j] = 0;
+            if (j < tiles) {
+                const int q = lo + j * 1024 + tid;
+                bool surv = false;
+                if (q < n) {
+                    const int p = q == m ? pi : s_perm[q];
+                    float s = q == m ? si : s_sc[q];
+                    float ov;
+                    surv = true;
+                    if (guarded_overlap(t, boxes[p], &ov)) {
+                        s = soft_decay(kind, ov, nt, sigma, s);
+                        surv = !(s < min_score);                        // cython_nms.pyx:191, inside the overlap branch
+                    }
+                    if (q == m) s_perm[q] = p;
+                    s_sc[q] = s;
+                }
+                bal[j] = __ballot(surv);
+                if (lane == 0) s_wcnt[j * 16 + wave] = (int)__popcll(bal[j]);
+            }
+        }
+        __syncthreads();
+        // survivors before each (tile, wave): every wave scans the <= 128 counts itself
+        const int nc = tiles * 16;
+        const int v0 = lane < nc ? s_wcnt[lane] : 0, v1 = lane + 64 < nc ? s_wcnt[lane + 64] : 0;
+        int i0 = v0, i1 = v1;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int x0 = __shfl_up(i0, o), x1 = __shfl_up(i1, o);
+            if (lane >= o) {
+                i0 += x0;
+                i1 += x1;
+            }
+        }
+        i1 += __shfl(i0, 63);
+        const int M = __shfl(i1, 63);
+        const int e0 = i0 - v0, e1 = i1 - v1;
+        int pre[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            pre[j] = 0;
+            if (j < tiles) {
+                const int at = j * 16 + wave;
+                const int a0 = __shfl(e0, at & 63), a1 = __shfl(e1, at & 63);
+                pre[j] = (at < 64 ? a0 : a1) + (int)__popcll(bal[j] & below);
+                const int q = lo + j * 1024 + tid;
+                if (q < n && !((bal[j] >> lane) & 1ull) && q < lo + M) s_hole[(q - lo) - pre[j]] = (unsigned short)q;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (j < tiles) {
+                const int q = lo + j * 1024 + tid;
+                if (q < n && ((bal[j] >> lane) & 1ull) && q >= lo + M) {
+                    const int dst = s_hole[M - pre[j] - 1];
+                    s_perm[dst] = s_perm[q];
+                    s_sc[dst] = s_sc[q];
+                }
+            }
+        }
+        n = lo + M;
+        __syncthreads();
+    }
+    if (tid == 0) scnt[c] = n;
+}
+
+// the greedy pass's kept bits of class c as records in ascending proposal order (dets_j[keep, :])
+__global__ __launch_bounds__(1024) void softvote_from_keep_kernel(const float* __restrict__ scores, int ld, int N, int W,
+                                                                  const unsigned long long* __restrict__ keepbits,
+                                                                  int* __restrict__ srec, int* __restrict__ scnt) {
+    __shared__ int s_part[16];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    unsigned long long word = tid < W ? keepbits[(size_t)c * W + tid] : 0ull;      // W <= 128
+    int tot;
+    int o = block_exclusive_scan((int)__popcll(word), s_part, &tot);
+    int* rec = srec + 3 * (size_t)c * N;
+    while (word) {
+        const int p = tid * 64 + __builtin_ctzll(word);
+        word &= word - 1;
+        rec[3 * o] = p;
+        rec[3 * o + 1] = c;
+        rec[3 * o + 2] = __float_as_int(scores[(size_t)p * ld + c]);
+        ++o;
+    }
+    if (tid == 0) scnt[c] = tot;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {                  // a fixed tree: the same bits on every run
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// boxes.py:268-317.  One wave per top detection; class c = blockIdx.y, top t of the class: record srec[c * cap + t], its box
+// top_boxes[c * cap + t] or, with top_boxes null, the record's proposal.  The voters are the class's candidates
+// (scores[p, c] > score_thr; every row with use_thr == 0) whose fp32 overlap with the top box is >= vote_thr.  Sums are
+// taken in double, lane-strided and then over the fixed tree above.  Writes the voted box, and the score by `method`
+// (ID: untouched) to out_score[(c * cap + t) * score_stride]; an empty vote set (or weights summing to 0: np.average's
+// ZeroDivisionError) writes NaN and counts in *empty.
+__global__ __launch_bounds__(256) void softvote_vote_kernel(const float* __restrict__ scores, int ld,
+                                                            const float4* __restrict__ boxes, int N, float score_thr,
+                                                            int use_thr, float vote_thr, int method, float beta,
+                                                            const float4* __restrict__ top_boxes,
+                                                            const int* __restrict__ srec, const int* __restrict__ scnt,
+                                                            int T, int cap, float4* __restrict__ vbox,
+                                                            float* __restrict__ out_score, int score_stride,
+                                                            int* __restrict__ empty) {
+    const int c = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cnt = scnt ? scnt[c] : T;
+    const double dbeta = (double)beta;
+    for (int t = blockIdx.x * 4 + wave; t < cnt; t += gridDim.x * 4) {
+        const size_t r = (size_t)c * cap + t;
+        const float4 tb = top_boxes ? top_boxes[r] : boxes[srec[3 * r]];
+        double sx1 = 0, sy1 = 0, sx2 = 0, sy2 = 0, sw = 0, sov = 0, sovw = 0, sp = 0, st = 0, cn = 0;
+        for (int p = lane; p < N; p += 64) {
+            const float s = scores[(size_t)p * ld + c];
+            if (use_thr && !(s > score_thr)) continue;
+            const float4 b = boxes[p];
+            float ov = 0.0f;
+            if (!guarded_overlap(tb, b, &ov)) ov = 0.0f;
+            if (!(ov >= vote_thr)) continue;
+            const double w = (double)s;
+            sx1 += w * (double)b.x;
+            sy1 += w * (double)b.y;
+            sx2 += w * (double)b.z;
+            sy2 += w * (double)b.w;
+            sw += w;
+            cn += 1.0;
+            if (method == CIM_SOFTVOTE_SCORE_IOU_AVG) {
+                sov += (double)ov;
+                sovw += (double)ov * w;
+            } else if (method == CIM_SOFTVOTE_SCORE_GENERALIZED_AVG) {
+                sp += pow(w, dbeta);
+            } else if (method == CIM_SOFTVOTE_SCORE_TEMP_AVG) {       // boxes.py:292-297 for one voter
+                const double a = w, nb = 1.0 - w, mx = a >= nb ? a : nb;
+                const double xa = exp(log(a / mx) / dbeta), xb = exp(log(nb / mx) / dbeta);
+                st += xa / (xa + xb);
+            }
+        }
+        sx1 = wave_sum(sx1);
+        sy1 = wave_sum(sy1);
+        sx2 = wave_sum(sx2);
+        sy2 = wave_sum(sy2);
+        sw = wave_sum(sw);
+        cn = wave_sum(cn);
+        if (method == CIM_SOFTVOTE_SCORE_IOU_AVG) {
+            sov = wave_sum(sov);
+            sovw = wave_sum(sovw);
+        } else if (method == CIM_SOFTVOTE_SCORE_GENERALIZED_AVG) {
+            sp = wave_sum(sp);
+        } else if (method == CIM_SOFTVOTE_SCORE_TEMP_AVG) {
+            st = wave_sum(st);
+        }
+        if (lane != 0) continue;
+        bool bad = cn == 0.0 || sw == 0.0;
+        double score = 0.0;
+        if (!bad) {
+            if (method == CIM_SOFTVOTE_SCORE_AVG) score = sw / cn;
+            else if (method == CIM_SOFTVOTE_SCORE_IOU_AVG) {
+                bad = sov == 0.0;
+                score = sovw / sov;
+            } else if (method == CIM_SOFTVOTE_SCORE_QUASI_SUM) score = sw / pow(cn, dbeta);
+            else if (method == CIM_SOFTVOTE_SCORE_GENERALIZED_AVG) score = pow(sp / cn, 1.0 / dbeta);
+            else if (method == CIM_SOFTVOTE_SCORE_TEMP_AVG) score = st / cn;
+        }
+        if (bad) {
+            const float nan = __int_as_float(0x7fc00000);
+            vbox[r] = make_float4(nan, nan, nan, nan);
+            if (method != CIM_SOFTVOTE_SCORE_ID) out_score[r * score_stride] = nan;
+            atomicAdd(empty, 1);
+        } else {
+            vbox[r] = make_float4((float)(sx1 / sw), (float)(sy1 / sw), (float)(sx2 / sw), (float)(sy2 / sw));
+            if (method != CIM_SOFTVOTE_SCORE_ID) out_score[r * score_stride] = (float)score;
+        }
+    }
+}
+
+// test.py:399-408 over the per-class records (after voting: the limit sees the re-scored detections): one workgroup.
+// Record order is preserved; boxes are the voted ones (vbox) or, with vbox null, the proposals'.
+__global__ __launch_bounds__(1024) void softvote_limit_kernel(const float4* __restrict__ boxes, int C, int cap, int max_det,
+                                                              const int* __restrict__ srec, const int* __restrict__ scnt,
+                                                              const float4* __restrict__ vbox, uint32_t* __restrict__ lkey,
+                                                              int* __restrict__ lsrc, int* __restrict__ det,
+                                                              float4* __restrict__ det_boxes, int* __restrict__ count,
+                                                              int* __restrict__ total) {
+    __shared__ int s_part[16];
+    const int tid = threadIdx.x;
+    for (int c = tid; c < C; c += 1024) count[c] = 0;
+    __threadfence();                                                   // (the zeros reach L2 before any atomic below)
+    int T = 0;
+    for (int c = 0; c < C; ++c) {
+        const int cnt = scnt[c];
+        for (int i = tid; i < cnt; i += 1024) {
+            const int r = c * cap + i;                                 // < C * N <= INT_MAX / 3
+            lkey[T + i] = orderable(__int_as_float(srec[3 * (size_t)r + 2]));
+            lsrc[T + i] = r;
+        }
+        T += cnt;
+    }
+    __syncthreads();
+    const uint32_t thr_key = limit_threshold(lkey, T, max_det);
+    int outn = 0;
+    for (int base = 0; base < T; base += 1024) {
+        const int i = base + tid;
+        const bool on = i < T && lkey[i] >= thr_key;
+        int tot;
+        const int o = outn + block_exclusive_scan(on ? 1 : 0, s_part, &tot);
+        if (on) {
+            const int r = lsrc[i];
+            const int p = srec[3 * (size_t)r], c = srec[3 * (size_t)r + 1];
+            det[3 * (size_t)o] = p;
+            det[3 * (size_t)o + 1] = c;
+            det[3 * (size_t)o + 2] = srec[3 * (size_t)r + 2];
+            det_boxes[o] = vbox ? vbox[r] : boxes[p];
+            atomicAdd(count + c, 1);
+        }
+        outn += tot;
+    }
+    if (tid == 0) *total = outn;
+}
+
+struct SoftvoteLayout {
+    DetectLayout d;
+    size_t srec, scnt, vbox, total;
+};
+
+SoftvoteLayout softvote_layout(int N, int C) {
+    const size_t cap = (size_t)C * N;
+    SoftvoteLayout L;
+    L.d = layout(N, C);
+    L.srec = (L.d.total + 255) & ~(size_t)255;
+    L.scnt = L.srec + ((cap * 12 + 255) & ~(size_t)255);
+    L.vbox = L.scnt + (((size_t)C * 4 + 255) & ~(size_t)255);
+    L.total = L.vbox + cap * 16;
+    return L;
+}
+
+bool nms_kind_ok(int k) { return k >= CIM_SOFTVOTE_NMS_GREEDY && k <= CIM_SOFTVOTE_NMS_SOFT_GAUSSIAN; }
+bool scoring_ok(int m) { return m >= CIM_SOFTVOTE_SCORE_ID && m <= CIM_SOFTVOTE_SCORE_TEMP_AVG; }
+
+}  // namespace
+
+extern "C" long long cim_softvote_ws_bytes(int N, int C) {
+    if (!shape_ok(N, C)) {
+        cim::set_error("cim_softvote_ws_bytes: need 1 <= N <= %d and C >= 1 with 3 * C * N < 2^31 (N=%d, C=%d)", kMaxN, N, C);
+        return -1;
+    }
+    return (long long)softvote_layout(N, C).total;
+}
+
+extern "C" int cim_softvote_postprocess(const float* scores, int ld, const float* boxes, int N, int C, float score_thr,
+                                        float nms_thr, int nms_kind, float sigma, float soft_min_score, int vote,
+                                        float vote_thr, int scoring_method, float beta, int max_det, void* ws, int* det,
+                                        float* det_boxes, int* count_per_class, int* total, int* empty_votes, void* stream) {
+    if (!shape_ok(N, C)) {
+        cim::set_error("cim_softvote_postprocess: need 1 <= N <= %d and C >= 1 with 3 * C * N < 2^31 (N=%d, C=%d)", kMaxN, N, C);
+        return -1;
+    }
+    if (!nms_kind_ok(nms_kind) || !scoring_ok(scoring_method)) {
+        cim::set_error("cim_softvote_postprocess: unknown nms_kind %d or scoring_method %d", nms_kind, scoring_method);
+        return -1;
+    }
+    if (vote && !(score_thr >= 0.0f)) {                                // the voters' scores are the weights of the mean
+        cim::set_error("cim_softvote_postprocess: voting needs score_thr >= 0 (score_thr=%g)", (double)score_thr);
+        return -1;
+    }
+    CIM_CHECK_ARG(ld >= C);
+    CIM_CHECK_ARG(scores && boxes && ws && det && det_boxes && count_per_class && total && empty_votes);
+    CIM_CHECK_ARG(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)ws & 15) == 0 && ((uintptr_t)det_boxes & 15) == 0);
+    hipStream_t st = cim::as_stream(stream);
+    const int W = (N + 63) / 64;
+    const SoftvoteLayout L = softvote_layout(N, C);
+    char* w = static_cast<char*>(ws);
+    const float4* bx = reinterpret_cast<const float4*>(boxes);
+    int* srec = reinterpret_cast<int*>(w + L.srec);
+    int* scnt = reinterpret_cast<int*>(w + L.scnt);
+    float4* vbox = reinterpret_cast<float4*>(w + L.vbox);
+    CIM_CHECK_HIP(hipMemsetAsync(empty_votes, 0, sizeof(int), st));
+    if (nms_kind == CIM_SOFTVOTE_NMS_GREEDY) {
+        auto* mat = reinterpret_cast<unsigned long long*>(w + L.d.mat);
+        auto* keep = reinterpret_cast<unsigned long long*>(w + L.d.keep);
+        hipLaunchKernelGGL(detect_overlap_kernel, dim3(W, W), dim3(64), 0, st, bx, N, W, nms_thr, mat);
+        CIM_CHECK_LAUNCH();
+        int P = 1;
+        while (P < N) P <<= 1;
+        const int lds = P * 8;
+        CIM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(detect_nms_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        hipLaunchKernelGGL(detect_nms_kernel, dim3(C), dim3(1024), lds, st, scores, ld, bx, N, W, score_thr, nms_thr, mat, keep);
+        CIM_CHECK_LAUNCH();
+        hipLaunchKernelGGL(softvote_from_keep_kernel, dim3(C), dim3(1024), 0, st, scores, ld, N, W, keep, srec, scnt);
+        CIM_CHECK_LAUNCH();
+    } else {
+        const int lds = 8 * N + 2 * (N / 2 + 1) + 2;
+        CIM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(softvote_soft_nms_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        hipLaunchKernelGGL(softvote_soft_nms_kernel, dim3(C), dim3(1024), lds, st, scores, ld, bx, N, score_thr, nms_thr, sigma,
+                           soft_min_score, nms_kind, srec, scnt);
+        CIM_CHECK_LAUNCH();
+    }
+    if (vote) {
+        hipLaunchKernelGGL(softvote_vote_kernel, dim3(std::min(64, (N + 3) / 4), C), dim3(256), 0, st, scores, ld, bx, N, score_thr, 1,
+                           vote_thr, scoring_method, beta, (const float4*)nullptr, srec, scnt, 0, N, vbox,
+                           reinterpret_cast<float*>(srec) + 2, 3, empty_votes);
+        CIM_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(softvote_limit_kernel, dim3(1), dim3(1024), 0, st, bx, C, N, max_det, srec, scnt,
+                       vote ? vbox : (const float4*)nullptr, reinterpret_cast<uint32_t*>(w + L.d.lkey),
+                       reinterpret_cast<int*>(w + L.d.lidx), det, reinterpret_cast<float4*>(det_boxes), count_per_class, total);
+    CIM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int cim_softvote_vote(const float* all_boxes, const float* all_scores, int K, const float* top_boxes, int T,
+                                 float vote_thr, int scoring_method, float beta, float* out_boxes, float* out_scores,
+                                 int* empty_votes, void* stream) {
+    if (K < 1 || T < 1 || !scoring_ok(scoring_method)) {
+        cim::set_error("cim_softvote_vote: need K >= 1 voters, T >= 1 top boxes and a known scoring method (K=%d, T=%d, "
+                       "scoring_method=%d)", K, T, scoring_method);
+        return -1;
+    }
+    CIM_CHECK_ARG(all_boxes && all_scores && top_boxes && out_boxes && out_scores && empty_votes);
+    CIM_CHECK_ARG(((uintptr_t)all_boxes & 15) == 0 && ((uintptr_t)top_boxes & 15) == 0 && ((uintptr_t)out_boxes & 15) == 0);
+    hipStream_t st = cim::as_stream(stream);
+    CIM_CHECK_HIP(hipMemsetAsync(empty_votes, 0, sizeof(int), st));
+    hipLaunchKernelGGL(softvote_vote_kernel, dim3(std::min(1024, (T + 3) / 4), 1), dim3(256), 0, st, all_scores, 1,
+                       reinterpret_cast<const float4*>(all_boxes), K, 0.0f, 0, vote_thr, scoring_method, beta,
+                       reinterpret_cast<const float4*>(top_boxes), (const int*)nullptr, (const int*)nullptr, T, T,
+                       reinterpret_cast<float4*>(out_boxes), out_scores, 1, empty_votes);
     CIM_CHECK_LAUNCH();
     return 0;
 }

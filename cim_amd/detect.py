@@ -4,6 +4,7 @@ and the per-class argmax of CorLoc (csrc/detect.hip).
 Replaces the host loops of lib/core/test.py:320-420 and lib/utils/mask_eval_utils.py:6-108 over the
 compiled lib/utils/cython_nms.pyx.  Takes and returns DEVICE tensors and launches on the current stream; a CPU tensor is an
 error (no CPU fallback).  `to_host` / `corloc_host` make the one device-to-host copy a caller of host results needs.
+`postprocess` / `softvote_to_host` / `box_voting` are the same stage under TEST.SOFT_NMS / TEST.BBOX_VOTE.
 The reference-shaped wrappers are cim_amd.core.test, cim_amd.utils.mask_eval_utils and cim_amd.utils.boxes.
 """
 import collections
@@ -276,3 +277,101 @@ def device_inputs(scores, boxes, boxes_on_device=True):
         boxes_h = np.ascontiguousarray(np.asarray(boxes), dtype=np.float32)
         boxes_d = torch.from_numpy(boxes_h).to(dev) if boxes_on_device else None
     return scores, boxes_d, boxes_h
+
+
+# ---------------------------------------------------------------- soft-NMS and box voting
+SOFT_NMS_METHODS = {"hard": _lib.CONSTANTS["CIM_SOFTVOTE_NMS_SOFT_HARD"], "linear": _lib.CONSTANTS["CIM_SOFTVOTE_NMS_SOFT_LINEAR"],
+                    "gaussian": _lib.CONSTANTS["CIM_SOFTVOTE_NMS_SOFT_GAUSSIAN"]}
+SCORING_METHODS = {m: _lib.CONSTANTS["CIM_SOFTVOTE_SCORE_" + m]
+                   for m in ("ID", "AVG", "IOU_AVG", "QUASI_SUM", "GENERALIZED_AVG", "TEMP_AVG")}
+
+# device results: `buf` int32 [total | empty votes | count_per_class[C] | det[C * N][3]], `boxes` f32 [C * N, 4]
+SoftDetections = collections.namedtuple("SoftDetections", "buf boxes num_classes max_det")
+
+
+def _scoring(method):
+    if method not in SCORING_METHODS:
+        raise NotImplementedError("Unknown scoring method {}".format(method))          # boxes.py:313-315
+    return SCORING_METHODS[method]
+
+
+def postprocess(scores, boxes, score_thr=1e-5, nms_thr=0.3, max_det=100, soft_nms=None, box_vote=None, num_classes=None):
+    """`nms_limit` with TEST.SOFT_NMS and / or TEST.BBOX_VOTE (lib/core/test.py:378-396), on the device.
+
+    soft_nms: None (the greedy pass of `nms_limit`) or dict(method='hard' | 'linear' | 'gaussian', sigma=0.5,
+    min_score=0.0001): per class the reference's swap-based loop on the candidates in ascending proposal order; records come
+    in SELECTION order with the DECAYED scores, bit for bit the reference's.  box_vote: None or dict(thresh=0.8,
+    scoring_method='ID', beta=1.0): every kept box becomes the score-weighted mean of the class's candidates overlapping it
+    by >= thresh, its score follows scoring_method; needs score_thr >= 0.  The limit over all classes comes last, on the
+    decayed / re-scored values.  Returns SoftDetections (device buffers; see `softvote_to_host`).  Launches on the current
+    stream, does not synchronise."""
+    kind, sigma, min_score = _lib.CONSTANTS["CIM_SOFTVOTE_NMS_GREEDY"], 0.5, 0.0001
+    if soft_nms is not None:
+        method = soft_nms.get("method", "linear")
+        assert method in SOFT_NMS_METHODS, "Unknown soft_nms method: {}".format(method)  # boxes.py:335
+        kind, sigma, min_score = SOFT_NMS_METHODS[method], soft_nms.get("sigma", 0.5), soft_nms.get("min_score", 0.0001)
+    vote, vote_thr, scoring, beta = 0, 0.8, 0, 1.0
+    if box_vote is not None:
+        vote, vote_thr = 1, box_vote.get("thresh", 0.8)
+        scoring, beta = _scoring(box_vote.get("scoring_method", "ID")), box_vote.get("beta", 1.0)
+        if not np.float32(score_thr) >= 0:
+            raise ValueError("cim_amd.detect: box voting needs score_thr >= 0 (the voters' scores are the weights of a mean), "
+                             "got %r" % (score_thr,))
+    scores, n, C = _scores(scores, num_classes)
+    boxes = _boxes(boxes, n, scores.device)
+    ws_bytes = _lib.call("cim_softvote_ws_bytes", n, C)
+    if ws_bytes < 0:
+        raise ValueError(_lib.load().cim_last_error().decode())
+    ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=scores.device)
+    buf = torch.empty(2 + C + 3 * C * n, dtype=torch.int32, device=scores.device)
+    out_boxes = torch.empty((C * n, 4), dtype=torch.float32, device=scores.device)
+    base = buf.data_ptr()
+    _lib.call("cim_softvote_postprocess", scores.data_ptr(), scores.stride(0), boxes.data_ptr(), n, C, float(score_thr),
+              float(nms_thr), kind, float(sigma), float(min_score), vote, float(vote_thr), scoring, float(beta), int(max_det),
+              ws.data_ptr(), base + 4 * (2 + C), out_boxes.data_ptr(), base + 8, base, base + 4, _lib.stream_ptr())
+    return SoftDetections(buf, out_boxes, C, int(max_det))
+
+
+def softvote_to_host(det):
+    """SoftDetections -> NumPy (idx int64 [T], cls int32 [T], score f32 [T], count_per_class int32 [C], boxes f32 [T, 4]),
+    records in class order, within a class in the reference's.  One device-to-host copy of the header, the first
+    max(max_det, 0) records and their boxes (all of them without a limit); a second only when ties at the limit's threshold
+    keep more than max_det.  Raises ZeroDivisionError, as the reference's np.average does, if a voted box had no voter."""
+    C = det.num_classes
+    head = 2 + C
+    cap = (det.buf.numel() - head) // 3
+    first = cap if det.max_det <= 0 else min(cap, det.max_det)
+    h = torch.cat([det.buf[:head + 3 * first], det.boxes[:first].reshape(-1).view(torch.int32)]).cpu().numpy()
+    total = int(h[0])
+    if int(h[1]):
+        raise ZeroDivisionError("Weights sum to zero, can't be normalized (%d voted boxes had no voter)" % int(h[1]))
+    rec, bx = h[head:head + 3 * first], h[head + 3 * first:]
+    if total > first:
+        more = torch.cat([det.buf[head + 3 * first:head + 3 * total],
+                          det.boxes[first:total].reshape(-1).view(torch.int32)]).cpu().numpy()
+        rec, bx = np.concatenate([rec, more[:3 * (total - first)]]), np.concatenate([bx, more[3 * (total - first):]])
+    rec = rec[:3 * total].reshape(total, 3)
+    return (rec[:, 0].astype(np.int64), rec[:, 1].copy(), rec[:, 2].view(np.float32).copy(), h[2:head].copy(),
+            bx[:4 * total].view(np.float32).reshape(total, 4).copy())
+
+
+def box_voting(top_boxes, all_boxes, all_scores, thresh, scoring_method="ID", beta=1.0):
+    """lib/utils/boxes.py:268-317 for arbitrary top boxes: top_boxes [T, 4], all_boxes [K, 4], all_scores [K], device f32
+    tensors.  Returns device (boxes [T, 4], scores [T] - written unless scoring_method is 'ID' -, empty int32 [1]: top boxes
+    without a voter, which the reference answers with ZeroDivisionError)."""
+    scoring = _scoring(scoring_method)
+    for t in (top_boxes, all_boxes, all_scores):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise _lib.CimHipError("cim_amd.detect: box_voting takes CUDA/HIP tensors (no CPU fallback)")
+    T, K = int(top_boxes.shape[0]), int(all_boxes.shape[0])
+    if tuple(top_boxes.shape) != (T, 4) or tuple(all_boxes.shape) != (K, 4) or tuple(all_scores.shape) != (K,) or T < 1 or K < 1:
+        raise ValueError("cim_amd.detect: box_voting takes top_boxes [T, 4], all_boxes [K, 4], all_scores [K] with T, K >= 1")
+    top = top_boxes.to(torch.float32).contiguous()
+    allb = all_boxes.to(torch.float32).contiguous()
+    alls = all_scores.to(torch.float32).contiguous()
+    out_b = torch.empty((T, 4), dtype=torch.float32, device=top.device)
+    out_s = torch.zeros(T, dtype=torch.float32, device=top.device)
+    empty = torch.empty(1, dtype=torch.int32, device=top.device)
+    _lib.call("cim_softvote_vote", allb.data_ptr(), alls.data_ptr(), K, top.data_ptr(), T, float(thresh), scoring, float(beta),
+              out_b.data_ptr(), out_s.data_ptr(), empty.data_ptr(), _lib.stream_ptr())
+    return out_b, out_s, empty

@@ -285,6 +285,48 @@ int cim_batch_detect_nms_limit(const float* scores, int ld, const float* boxes, 
                                const float* area_bounds, const unsigned char* class_mask, void* ws, int32_t* det,
                                int32_t* count, int32_t* total, void* stream);
 
+/* Soft-NMS and box voting (additive: cim_abi_version() stays 16): TEST.SOFT_NMS / TEST.BBOX_VOTE of
+ * box_results_with_nms_and_limit (lib/core/test.py:378-396) - cython_nms.pyx:98-203 (soft_nms), boxes.py:268-317
+ * (box_voting) over cython_bbox.pyx:32-73 (bbox_overlaps) - followed by the same per-image limit.  Same inputs, shape limits
+ * and refusals as cim_detect_nms_limit.
+ *   nms_kind   CIM_SOFTVOTE_NMS_GREEDY: the greedy pass of cim_detect_nms_limit (its bits, its tie rule).  SOFT_HARD / LINEAR /
+ *              GAUSSIAN: per class, on the candidates s > score_thr in ascending proposal order, the pyx's loop - select the
+ *              FIRST position of the maximum score, swap it forward, decay every later row that overlaps it (iw > 0 and ih > 0)
+ *              by the method's weight (overlap threshold nms_thr, gaussian: (float)exp((double)(-(ov * ov) / sigma))), drop a
+ *              decayed row whose score is < soft_min_score by overwriting it with the last row.  A row that overlaps nothing is
+ *              never dropped.  Records come in SELECTION order with the DECAYED scores, bit for bit the pyx's (fp32 operation
+ *              for operation, ties by array position), given finite boxes and a device exp() that rounds to the same fp32.
+ *   vote       nonzero: every record's box becomes the score-weighted mean of the class's candidates whose fp32 overlap with
+ *              it is >= vote_thr, and its score follows scoring_method (CIM_SOFTVOTE_SCORE_*, beta as in boxes.py); sums are
+ *              taken in double in a fixed order (the same bits on every run and stream).  Needs score_thr >= 0 (weights > 0).
+ *              A record with no voter gets NaN and adds 1 to *empty_votes (the reference raises ZeroDivisionError there).
+ *   max_det    the limit over all classes AFTER soft-NMS / voting, on the decayed / re-scored values; record order is kept.
+ *   ws         cim_softvote_ws_bytes(N, C) bytes, 16-byte aligned, no initial content.
+ * Outputs: det [C * N][3] i32 records (proposal, class, score bit pattern), class ascending, within a class the order above;
+ * det_boxes [C * N][4] f32 (16-byte aligned) the records' boxes - voted, or the proposals' -; count_per_class [C]; total [1];
+ * empty_votes [1].  One memset and 3 - 5 launches, no host synchronisation. */
+#define CIM_SOFTVOTE_NMS_GREEDY 0
+#define CIM_SOFTVOTE_NMS_SOFT_HARD 1
+#define CIM_SOFTVOTE_NMS_SOFT_LINEAR 2
+#define CIM_SOFTVOTE_NMS_SOFT_GAUSSIAN 3
+#define CIM_SOFTVOTE_SCORE_ID 0
+#define CIM_SOFTVOTE_SCORE_AVG 1
+#define CIM_SOFTVOTE_SCORE_IOU_AVG 2
+#define CIM_SOFTVOTE_SCORE_QUASI_SUM 3
+#define CIM_SOFTVOTE_SCORE_GENERALIZED_AVG 4
+#define CIM_SOFTVOTE_SCORE_TEMP_AVG 5
+long long cim_softvote_ws_bytes(int N, int C);
+int cim_softvote_postprocess(const float* scores, int ld, const float* boxes, int N, int C, float score_thr, float nms_thr,
+                             int nms_kind, float sigma, float soft_min_score, int vote, float vote_thr, int scoring_method,
+                             float beta, int max_det, void* ws, int32_t* det, float* det_boxes, int32_t* count_per_class,
+                             int32_t* total, int32_t* empty_votes, void* stream);
+/* box_voting on arbitrary top boxes: all_boxes [K][4] and all_scores [K] vote (every row, scores as weights) for top_boxes
+ * [T][4]; out_boxes [T][4] the voted boxes, out_scores [T] the scores by scoring_method (left untouched for ID), empty_votes
+ * [1] as above.  K >= 1, T >= 1; the box arrays 16-byte aligned.  One memset and one launch. */
+int cim_softvote_vote(const float* all_boxes, const float* all_scores, int K, const float* top_boxes, int T, float vote_thr,
+                      int scoring_method, float beta, float* out_boxes, float* out_scores, int32_t* empty_votes,
+                      void* stream);
+
 /* ------------------------------------------------------------------ instance-segmentation evaluation (ABI-16 addition)
  * Replaces pycocotools' mask.encode / decode / iou and COCOeval(..., 'segm').evaluateImg / accumulate as the reference runs
  * them (tools/evaluation.py:72-145, 236-241; lib/datasets/json_inference.py:24-55; lib/utils/mask_eval_utils.py:113-116).
