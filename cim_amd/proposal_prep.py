@@ -132,6 +132,38 @@ def assign_clusters(prep, rows, cols, classes, num_classes):
     return mat
 
 
+def label_assign(model, images_u8, labels, masks_list, mask_size=7):
+    """tools/pre/AGPL_label_assign.py `assign_voc2012` / `assign_coco2017` for a batch of images, without the reference:
+    model = a cim_amd.prm.PeakResponseMapping on the device, images_u8 = B RGB uint8 arrays [h, w, 3] (host; what
+    Image.open(...).convert('RGB') holds), labels = B lists of image-level classes (ascending, as torch.unique leaves them),
+    masks_list = B device tensors [N_i, h, w] of the image's proposal masks.  Returns B cluster matrices `mat`
+    [N_i, num_classes + 1] float32 on the device (21 or 81 columns by the model's classifier).
+    The antialiased transforms.Resize([448, 448]) is Pillow's own call on the host (a device restatement of Pillow's resize is
+    out of scope); everything behind it runs on the device with ONE host read per batch (cim_amd.prm.peaks) plus `prepare`'s
+    empty-mask flag per image.  An image without classes gets the reference's `visual_cues == None` matrix (column 0 = 1)."""
+    from PIL import Image
+
+    from . import prm
+    b = len(images_u8)
+    if not (len(labels) == b and len(masks_list) == b):
+        raise ValueError("cim_amd.proposal_prep.label_assign: %d images, %d class lists, %d mask tensors" % (b, len(labels), len(masks_list)))
+    size = prm.INPUT_SIZE
+    resized = np.stack([np.asarray(Image.fromarray(np.ascontiguousarray(im, dtype=np.uint8)).resize((size, size), Image.BILINEAR))
+                        for im in images_u8])
+    sizes = [(int(m.shape[1]), int(m.shape[2])) for m in masks_list]
+    if any(len(ls) for ls in labels):
+        inputs = prm.network_input(torch.from_numpy(resized).to(masks_list[0].device))
+        points = prm.peaks(model, inputs, labels, image_sizes=sizes)
+    else:
+        points = [((), (), (), ())] * b
+    num_classes = model[0].classifier[0].out_channels
+    mats = []
+    for masks, (rows, cols, classes, _) in zip(masks_list, points):
+        prep = prepare(masks, mask_size)
+        mats.append(assign_clusters(prep, rows, cols, classes, num_classes))
+    return mats
+
+
 def peaks_to_pixels(peak_list, height, width):
     """AGPL_label_assign.py:156-161: peak_list [P, 4] = (batch, class, a, b) on the PRM's 112 x 112 grid, already in ascending
     peak_score order -> (rows, cols, classes) with row = int(a * H / 112), col = int(b * W / 112) (the reference names them

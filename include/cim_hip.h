@@ -494,6 +494,48 @@ int cim_prop_prepare(const uint8_t* masks_u8, int N, int H, int W, int S, uint64
 int cim_prop_assign(const uint64_t* packed, const int32_t* area, int N, int H, int W, const int32_t* rows, const int32_t* cols,
                     const int32_t* classes, int P, int C, float* mat, void* ws, void* stream);
 
+/* ------------------------------------------------------------------ PRM peaks: class response maps to cluster points (ABI-16 addition)
+ * Replaces what tools/pre/AGPL_label_assign.py:136-161 reads from lib/prm/prm_model_gt.py:216-310 (PeakResponseMapping.forward
+ * in inference mode) and lib/prm/prm_modules.py:9-44 (PeakStimulation): the bilinear sub-pixel up-sampling of the class response
+ * maps, the median-filtered 3 x 3 peak test, the threshold / fallback selection and the ascending-score order, for a BATCH of
+ * images and only for the (image, class) PAIRS the caller names.  The peak back-propagation (the peak response maps) is not
+ * computed: the label assignment reads only their number.  Additive: cim_abi_version() stays 16.  Exactness contract: DESIGN.md 4.19.
+ *
+ * desc: int32 [2 M + 2 B] = pair image [M] | pair class [M] | image height [B] | image width [B]; the caller passes it twice,
+ * desc_host (HOST memory, read and checked before the call returns) and desc_dev (the same words in device memory, read by the
+ * kernels).  The pairs of an image are contiguous, images ascending, classes in the caller's order (the order of `lables`).
+ * Refused before any launch (-1, cim_last_error() names the condition): M < 1, B < 1, H W > CIM_PRM_MAX_HW, factor < 1, a class
+ * outside 0..C-1, an image index outside 0..B-1 or smaller than its predecessor, an image side outside 1..65535.
+ * ws: cim_prm_ws_bytes(M, HW) bytes, 8-byte aligned, no initial content, HW = 0 for cim_prm_peaks (which is given `up`).
+ *
+ * cim_prm_upsample: crm [B, C, h, w] f32 (+ bias [C] or NULL, added to every tap) -> up [M, factor h, factor w]: bilinear,
+ *   align_corners = True, the arithmetic of DESIGN.md 4.19 (bit-identical to tests/golden/prm_np.py: upsample).  One launch.
+ * cim_prm_peaks: up [M, H, W] f32 ->
+ *   median [M] f32           the LOWER median of each map (torch.median: element (H W - 1) / 2 of the ascending order),
+ *   pair_counts [M, 3] int32 all peaks (3 x 3 window, -inf padding, first maximum wins, value >= median) | valid peaks (value >
+ *                            peak_threshold; 1 when none is and the fallback - the first peak holding the largest peak value -
+ *                            stands in) | flags: CIM_PRM_STATUS_NAN, CIM_PRM_STATUS_NO_PEAK (a map of -inf only),
+ *   per image b: image_out [B, 2] int32 = number of valid peaks (the TRUE number, also beyond CIM_PRM_MAX_PEAKS) | status (0, or
+ *     CIM_PRM_STATUS_* bits; nothing else is written for an image whose status is not 0),
+ *     points [B, CIM_PRM_MAX_PEAKS, 5] int32 = (row, col, class, y, x) in ascending score order, STABLE (equal scores keep the
+ *     order pairs-then-row-major), row = y img_h / H, col = x img_w / W (integer division), scores [B, CIM_PRM_MAX_PEAKS] f32.
+ *   Two launches (one workgroup per pair, one per image); no host synchronisation, no atomics deciding an order.
+ * cim_prm_points: cim_prm_upsample into ws, then cim_prm_peaks on it: three launches. */
+#define CIM_PRM_MAX_HW (1 << 22)
+#define CIM_PRM_MAX_PEAKS (CIM_PROP_MAX_POINTS)   /* cim_prop_assign takes no more */
+#define CIM_PRM_STATUS_TOO_MANY 1
+#define CIM_PRM_STATUS_NAN 2
+#define CIM_PRM_STATUS_NO_PEAK 4
+long long cim_prm_ws_bytes(int M, int HW);
+int cim_prm_upsample(const float* crm, const float* bias, int B, int C, int h, int w, int factor, int M, const int32_t* desc_host,
+                     const int32_t* desc_dev, float* up, void* stream);
+int cim_prm_peaks(const float* up, int M, int H, int W, int B, int C, const int32_t* desc_host, const int32_t* desc_dev,
+                  float peak_threshold, float* median, int32_t* pair_counts, int32_t* points, float* scores, int32_t* image_out,
+                  void* ws, void* stream);
+int cim_prm_points(const float* crm, const float* bias, int B, int C, int h, int w, int factor, int M, const int32_t* desc_host,
+                   const int32_t* desc_dev, float peak_threshold, float* median, int32_t* pair_counts, int32_t* points,
+                   float* scores, int32_t* image_out, void* ws, void* stream);
+
 /* ------------------------------------------------------------------ network-input image (f-3: the data side of the step)
  * Replaces prep_im_for_blob(flag="ToTensor"), lib/utils/blob.py:93-147, called from lib/roi_data/minibatch.py:109-150
  * (training) and lib/core/test.py:464-473 via get_image_blob (inference):
