@@ -170,7 +170,8 @@ def peak_response_mapping_aff_vis(*a, **k):
 def network_input(rgb_u8):
     """ToTensor + Normalize of prm_configs.open_transform on the device: rgb_u8 [S, S', 3] (or [B, S, S', 3]) uint8, host or
     device -> [B, 3, S, S'] fp32.  cim_image_prep at scale 1 on the channel-swapped array: (x / 255 - mean) / std in fp32, bit for
-    bit (tests/test_gpu_prm.py).  The antialiased transforms.Resize([448, 448]) in front of it stays Pillow's call on the host."""
+    bit (tests/test_gpu_prm.py).  For images that still need the antialiased transforms.Resize([448, 448]) in front of it:
+    `network_input_from_images`."""
     t = rgb_u8 if torch.is_tensor(rgb_u8) else torch.from_numpy(np.ascontiguousarray(rgb_u8))
     if t.dtype != torch.uint8 or t.dim() not in (3, 4) or t.shape[-1] != 3:
         raise ValueError("cim_amd.prm.network_input: uint8 [H, W, 3] or [B, H, W, 3] (RGB) expected")
@@ -185,6 +186,15 @@ def network_input(rgb_u8):
         _lib.call("cim_image_prep", bgr[i].data_ptr(), h, w, out[i].data_ptr(), h, w, out.stride(1), out.stride(2), 1.0, 0,
                   ctypes.cast(_blob._MS, ctypes.c_void_p), _lib.stream_ptr())
     return out
+
+
+def network_input_from_images(images_u8, size=INPUT_SIZE, device=None):
+    """prm_configs.open_transform whole - transforms.Resize([size, size]) (Pillow's antialiased bilinear resize), ToTensor,
+    Normalize - on the device: images_u8 = uint8 [h_i, w_i, 3] RGB arrays of differing sizes (host NumPy or device tensors) ->
+    [B, 3, size, size] fp32, bit for bit `network_input` of Pillow's resized bytes (cim_amd.resample): three
+    launches for the batch, no host read.  `device`: where host images go (default: the current device)."""
+    from . import resample
+    return resample.pil_resize(images_u8, (int(size), int(size)), normalize=(_blob.MEAN, _blob.STD), device=device)
 
 
 class _Launch(object):

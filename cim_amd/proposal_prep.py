@@ -132,30 +132,38 @@ def assign_clusters(prep, rows, cols, classes, num_classes):
     return mat
 
 
-def label_assign(model, images_u8, labels, masks_list, mask_size=7):
+def label_assign(model, images_u8, labels, masks_list, mask_size=7, resize="device"):
     """tools/pre/AGPL_label_assign.py `assign_voc2012` / `assign_coco2017` for a batch of images, without the reference:
     model = a cim_amd.prm.PeakResponseMapping on the device, images_u8 = B RGB uint8 arrays [h, w, 3] (host; what
     Image.open(...).convert('RGB') holds), labels = B lists of image-level classes (ascending, as torch.unique leaves them),
     masks_list = B device tensors [N_i, h, w] of the image's proposal masks.  Returns B cluster matrices `mat`
     [N_i, num_classes + 1] float32 on the device (21 or 81 columns by the model's classifier).
-    The antialiased transforms.Resize([448, 448]) is Pillow's own call on the host (a device restatement of Pillow's resize is
-    out of scope); everything behind it runs on the device with ONE host read per batch (cim_amd.prm.peaks) plus `prepare`'s
-    empty-mask flag per image.  An image without classes gets the reference's `visual_cues == None` matrix (column 0 = 1)."""
-    from PIL import Image
-
+    resize = "device" (default): the antialiased transforms.Resize([448, 448]), ToTensor and Normalize are three launches for the
+    batch (cim_amd.prm.network_input_from_images, bit-identical to Pillow: DESIGN.md 4.20); "pillow": Pillow's own call on the
+    host, once per image, and an upload of the resized copy (kept for comparison; Pillow is imported on this path only).  The
+    results are the same bit for bit.  Everything runs on the device with ONE host read per batch (cim_amd.prm.peaks) plus
+    `prepare`'s empty-mask flag per image.  An image without classes gets the reference's `visual_cues == None` matrix
+    (column 0 = 1)."""
     from . import prm
     b = len(images_u8)
     if not (len(labels) == b and len(masks_list) == b):
         raise ValueError("cim_amd.proposal_prep.label_assign: %d images, %d class lists, %d mask tensors" % (b, len(labels), len(masks_list)))
+    if resize not in ("device", "pillow"):
+        raise ValueError("cim_amd.proposal_prep.label_assign: resize = %r, 'device' or 'pillow' expected" % (resize,))
     size = prm.INPUT_SIZE
-    resized = np.stack([np.asarray(Image.fromarray(np.ascontiguousarray(im, dtype=np.uint8)).resize((size, size), Image.BILINEAR))
-                        for im in images_u8])
     sizes = [(int(m.shape[1]), int(m.shape[2])) for m in masks_list]
-    if any(len(ls) for ls in labels):
-        inputs = prm.network_input(torch.from_numpy(resized).to(masks_list[0].device))
-        points = prm.peaks(model, inputs, labels, image_sizes=sizes)
-    else:
+    if not any(len(ls) for ls in labels):
         points = [((), (), (), ())] * b
+    else:
+        if resize == "pillow":
+            from PIL import Image
+            resized = np.stack([np.asarray(Image.fromarray(np.ascontiguousarray(im, dtype=np.uint8)).resize((size, size), Image.BILINEAR))
+                                for im in images_u8])
+            inputs = prm.network_input(torch.from_numpy(resized).to(masks_list[0].device))
+        else:
+            images = [im if torch.is_tensor(im) else np.ascontiguousarray(im, dtype=np.uint8) for im in images_u8]
+            inputs = prm.network_input_from_images(images, size, device=masks_list[0].device)
+        points = prm.peaks(model, inputs, labels, image_sizes=sizes)
     num_classes = model[0].classifier[0].out_channels
     mats = []
     for masks, (rows, cols, classes, _) in zip(masks_list, points):

@@ -536,6 +536,39 @@ int cim_prm_points(const float* crm, const float* bias, int B, int C, int h, int
                    const int32_t* desc_dev, float peak_threshold, float* median, int32_t* pair_counts, int32_t* points,
                    float* scores, int32_t* image_out, void* ws, void* stream);
 
+/* ------------------------------------------------------------------ Pillow's antialiased resize: raw RGB images to PRM inputs (ABI-16 addition)
+ * Replaces the host call Image.resize((448, 448), Image.BILINEAR) in front of the PRM (tools/pre/AGPL_label_assign.py through
+ * prm_configs.open_transform: transforms.Resize([448, 448]), ToTensor, Normalize) for a BATCH of images of differing sizes.
+ * Bit-identical to Pillow's src/libImaging/Resample.c on 8-bit RGB (tests/golden/pil_resample_np.py restates it): per axis a table
+ * of 22-bit fixed-point coefficients computed in IEEE double, the horizontal pass into a uint8 intermediate, then the vertical
+ * pass.  Additive: cim_abi_version() stays 16.  Exactness contract, the refusal and its reason: DESIGN.md 4.20.
+ *
+ * src: the images' bytes [h][w][3] (RGB, interleaved) anywhere in one device buffer.  desc: int64 [B][3] = (byte offset into
+ * src, h, w) per image; the caller passes it twice, desc_host (HOST memory, read and checked before the call returns) and
+ * desc_dev (the same words in device memory, read by the kernels).
+ * Refused before any launch (-1, cim_last_error() names the condition): B < 1 (or > 65535), a source side outside
+ * 1..CIM_RESAMPLE_MAX_SRC, an output side outside 1..CIM_RESAMPLE_MAX_DST, h > CIM_RESAMPLE_MAX_ASPECT w (Pillow runs the
+ * vertical pass first there, which changes the bytes), both destinations NULL, an offset before the end of the previous image.
+ * ws: cim_resample_ws_bytes(B, desc_host, out_w, out_h) bytes (-1 for a refused batch), 8-byte aligned, no initial content:
+ *   inter_off int64 [B] | bounds_x int32 [B][out_w][2] | bounds_y int32 [B][out_h][2] | coef_x int32 [B][out_w][KX] |
+ *   coef_y int32 [B][out_h][KY] | the uint8 intermediates [h][out_w][3], image after image;
+ *   bounds = (first source index, number of taps), KX / KY = the longest table row of the batch over the widths / heights,
+ *   a row of n_in -> n_out samples having 2 ceil(max(n_in / n_out, 1)) + 1 entries (those behind its taps are 0).
+ *
+ * cim_resample_tables: the table launch alone (one lane per image, axis and output index) into ws.
+ * cim_resample_rgb: tables, horizontal pass, vertical pass - three launches for any B, no host synchronisation - writing
+ *   dst_u8 [B][out_h][out_w][3] uint8 (Pillow's array) and / or dst_f32 [B][3][out_h][out_w] f32 =
+ *   ((float)byte / 255 - mean[c]) / std[c], the arithmetic of cim_image_prep; either may be NULL, not both.
+ *   mean_std6_host: six HOST floats (mean RGB, std RGB), needed with dst_f32. */
+#define CIM_RESAMPLE_MAX_SRC 16384
+#define CIM_RESAMPLE_MAX_DST 4096
+#define CIM_RESAMPLE_MAX_ASPECT 100
+#define CIM_RESAMPLE_PRECISION_BITS 22
+long long cim_resample_ws_bytes(int B, const int64_t* desc_host, int out_w, int out_h);
+int cim_resample_tables(const int64_t* desc_host, const int64_t* desc_dev, int B, int out_w, int out_h, void* ws, void* stream);
+int cim_resample_rgb(const uint8_t* src, const int64_t* desc_host, const int64_t* desc_dev, int B, int out_w, int out_h,
+                     uint8_t* dst_u8, float* dst_f32, const float* mean_std6_host, void* ws, void* stream);
+
 /* ------------------------------------------------------------------ network-input image (f-3: the data side of the step)
  * Replaces prep_im_for_blob(flag="ToTensor"), lib/utils/blob.py:93-147, called from lib/roi_data/minibatch.py:109-150
  * (training) and lib/core/test.py:464-473 via get_image_blob (inference):
