@@ -991,6 +991,12 @@ extern "C" long long cim_mining_lds_bytes(int N, int K) {
     return seed_layout(N, K).total;
 }
 
+extern "C" long long cim_mining_layout(int N, int K) {
+    if (N <= 0 || K <= 0) return 0;
+    const SeedLayout s = seed_layout(N, K);
+    return (long long)(s.det_lds | (s.row_lds << 1));
+}
+
 extern "C" long long cim_mining_sync_bytes(void) { return (long long)sizeof(MiningSync); }
 
 extern "C" int cim_mining_step(const cim_mining_args* args, void* sync, void* stream) {

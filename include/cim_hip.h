@@ -229,6 +229,10 @@ typedef struct cim_mining_args {
  * stream) and the call leaves every word zero again, so the same scratch serves the next call on that stream and the launches
  * can be captured into a HIP graph.  Calls that may be in flight TOGETHER (two streams) need a scratch each. */
 long long cim_mining_lds_bytes(int N, int K);
+/* Which form of the seed phase a call with these sizes runs (host only, additive: cim_abi_version() stays 16): bit 0 = the
+ * layer's detector column and flags are staged in LDS, bit 1 = the NMS bit-matrix comes from whole map rows streamed through LDS
+ * (else from K x K single gathers).  0 for N <= 0 or K <= 0. */
+long long cim_mining_layout(int N, int K);
 long long cim_mining_sync_bytes(void);
 int cim_mining_step(const cim_mining_args* args, void* sync, void* stream);
 

@@ -71,6 +71,9 @@ def cim_label(predict_cls, predict_det, label, iou_map, asy_iou_map, p_seed, nms
         keep_nms_idx = keep_sort_idx[keep_nms]                           # :380
         flag = (asy_iou_map[:, keep_nms_idx] > thr) & flag_all           # :386-390
         res_idx = np.zeros((0,), dtype=np.int64)
+        if trace is not None:            # per seed (column of :386, before :392 drops the empty ones): its arg-max, -1 for an empty column
+            per_seed = np.argmax(flag.astype(np.float32) * det_c[:, None], axis=0) if len(keep_nms_idx) else res_idx
+            trace.setdefault("res_per_seed", []).append(np.where(flag.sum(axis=0) > 0, per_seed, -1))
         if flag.sum() != 0:                                              # :391
             flag = flag[:, flag.sum(axis=0) > 0]                         # :392
             res_det = flag.astype(np.float32) * det_c[:, None]           # :393
@@ -120,6 +123,8 @@ def mist_label(preds, label, iou_map, p_seed, nms_thr, trace=None):
     gt_idxs = gt_labels.sum(axis=-1) > 0
     if trace is not None:
         trace["gt_idxs"] = gt_idxs.copy()
+        trace["gt_labels_full"] = gt_labels.copy()
+        trace["gt_weights_full"] = gt_weights.copy()
     return gt_labels[gt_idxs], gt_weights[gt_idxs], gt_idxs
 
 
@@ -178,6 +183,9 @@ def cim_layer_forward(predict_cls, predict_det, labels, iou_map, asy_iou_map,
     if gt_idxs.sum() == 0:                                                # :429
         return None, None, None
     overlaps = iou_map[:, gt_idxs]                                        # :435
+    if trace is not None:                # list length and members per class (in the order of np.nonzero(labels)) before the sampling
+        trace["class_members"] = [int((gt_labels[:, c + 1] == 1).sum()) for c in np.nonzero(labels.reshape(-1))[0]]
+        trace["class_weights"] = [gt_weights[gt_labels[:, c + 1] == 1].copy() for c in np.nonzero(labels.reshape(-1))[0]]
     if anti_noise_sampling:
         keep = anti_noise_sample(gt_labels, gt_weights, labels, rng)
         if trace is not None:
@@ -188,4 +196,5 @@ def cim_layer_forward(predict_cls, predict_det, labels, iou_map, asy_iou_map,
     pseudo_labels, pseudo_iou, loss_weights, max_i = assign(overlaps, gt_labels, gt_weights, cls_thr, iou_thr)
     if trace is not None:
         trace["max_overlap_idx"] = max_i.copy()
+        trace["overlaps"] = overlaps.copy()
     return pseudo_labels, pseudo_iou, loss_weights
