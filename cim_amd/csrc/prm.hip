@@ -9,11 +9,13 @@
 // all C maps and reads those in `lables`).  Three launches for a batch: up-sampling (one lane per output pixel), peaks (one
 // workgroup per pair), order (one workgroup per image).  VALU / LDS work, no MFMA, no scratch.
 #include "common.h"
+#include "prm_select.h"
 #include "../../include/cim_hip.h"
 
 namespace {
 
-constexpr int PRM_THREADS = 256;
+using cim::PRM_THREADS;
+using cim::prm_key;
 
 struct PeakEntry {
     int32_t pix;                                  // y * W + x on the up-sampled grid
@@ -52,19 +54,12 @@ __global__ __launch_bounds__(PRM_THREADS) void prm_upsample_kernel(const float* 
 }
 
 // ---- (b) median, peak test, ordered compaction, selection: one workgroup per pair ---------------------------------------------
-// Order-preserving 32-bit keys: ascending key order is ascending float order with -0.0 below +0.0 (integer work only).
-__device__ __forceinline__ unsigned prm_key(unsigned u) { return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ unsigned prm_unkey(unsigned k) { return (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; }
-
-__device__ __forceinline__ float prm_at(const float* __restrict__ map, int H, int W, int y, int x) {
-    return (y >= 0 && y < H && x >= 0 && x < W) ? map[y * W + x] : -INFINITY;      // ConstantPad2d(1, -inf)
-}
-
+// (keys, the radix select of the median and the 3 x 3 peak test: prm_select.h, shared with prm_train.hip)
 __global__ __launch_bounds__(PRM_THREADS) void prm_peaks_kernel(const float* __restrict__ up, int H, int W, float thr,
                                                                 float* __restrict__ median, int32_t* __restrict__ pair_counts,
                                                                 PeakEntry* __restrict__ plist) {
     __shared__ int hist[256];
-    __shared__ int s_bin, s_k, s_nan;
+    __shared__ int s_sel[2], s_nan;
     __shared__ int s_pk[PRM_THREADS / 64], s_va[PRM_THREADS / 64];
     __shared__ unsigned long long s_best;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -78,36 +73,7 @@ __global__ __launch_bounds__(PRM_THREADS) void prm_peaks_kernel(const float* __r
         s_nan = 0;
         s_best = 0ull;
     }
-    unsigned prefix = 0u, mask = 0u;
-    int k = (n - 1) >> 1;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        hist[tid] = 0;
-        __syncthreads();
-        bool nan = false;
-        for (int i = tid; i < n; i += PRM_THREADS) {
-            const unsigned u = bits[i];
-            nan = nan || (u & 0x7fffffffu) > 0x7f800000u;
-            const unsigned key = prm_key(u);
-            if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
-        }
-        if (shift == 24 && nan) s_nan = 1;
-        __syncthreads();
-        if (tid == 0) {
-            int c = 0, b = 0;
-            for (; b < 255; ++b) {
-                const int hb = hist[b];
-                if (k < c + hb) break;
-                c += hb;
-            }
-            s_bin = b;
-            s_k = k - c;
-        }
-        __syncthreads();
-        prefix |= (unsigned)s_bin << shift;
-        mask |= 255u << shift;
-        k = s_k;
-    }
-    const float med = __uint_as_float(prm_unkey(prefix));
+    const float med = __uint_as_float(cim::prm_lower_median_bits(bits, n, hist, s_sel, &s_nan));
 
     // peaks in row-major order; the valid ones (value > thr) are compacted in that order (ballot + prefix)
     int nvalid = 0, npeaks = 0;
@@ -119,10 +85,7 @@ __global__ __launch_bounds__(PRM_THREADS) void prm_peaks_kernel(const float* __r
         if (i < n) {
             const int y = i / W, x = i % W;
             v = map[i];
-            // max_pool2d keeps the FIRST maximum of the window (val > max): earlier neighbours strictly less, later ones <=
-            pk = v >= med && prm_at(map, H, W, y - 1, x - 1) < v && prm_at(map, H, W, y - 1, x) < v &&
-                 prm_at(map, H, W, y - 1, x + 1) < v && prm_at(map, H, W, y, x - 1) < v && prm_at(map, H, W, y, x + 1) <= v &&
-                 prm_at(map, H, W, y + 1, x - 1) <= v && prm_at(map, H, W, y + 1, x) <= v && prm_at(map, H, W, y + 1, x + 1) <= v;
+            pk = cim::prm_is_peak(map, H, W, y, x, v, med);
             va = pk && v > thr;
             if (pk) {                                                     // arg-max of the peak values: the first of the largest
                 unsigned u = __float_as_uint(v);

@@ -1,0 +1,192 @@
+"""PRM classification training on the device: peak stimulation and the multilabel soft margin loss.
+
+Replaces what lib/prm/prm_model.py composes for training - F.upsample(align_corners=True), the median filter,
+lib/prm/prm_modules.py `PeakStimulation` (forward and backward) and F.multilabel_soft_margin_loss - by the launches of
+csrc/prm_train.hip: one workgroup per (image, class) map up-samples it into LDS, finds its peaks and averages them; the backward
+gathers the peaks' tap weights into a gradient of the class response map's own size.  The body runs on the kernels the
+detector's body trains on.
+
+    model = prm.PeakResponseMapping(prm.fc_resnet50(num_classes=20))     # the same object `cim_amd.prm.peaks` takes
+    prm_train.freeze(model)                                              # stem and layer1, as the detector's body
+    loss = prm_train.loss(model, images, target)                         # images [B,3,S,S'] (prm.network_input*), target [B,C]
+    loss.backward()
+
+`cim_amd.prm.PeakResponseMapping` itself stays the inference object (its train() raises, its forward runs under no_grad): a
+checkpoint moves between the two entries unchanged.  BatchNorm statistics stay frozen (the reference's train() updates them),
+the stem never trains (its kernel is forward only).  Takes DEVICE tensors; a CPU tensor is an error (no CPU fallback)."""
+import numpy as np
+import torch
+from torch.autograd import Function
+
+from . import _lib
+from . import prm as _prm
+from .ops import conv1x1_bn_act, conv7x7_bn_act, max_pool2d
+
+STIM_MAX_HW = _lib.CONSTANTS["CIM_PRM_STIM_MAX_HW"]
+STATUS_NAN, STATUS_NO_PEAK = _prm.STATUS_NAN, _prm.STATUS_NO_PEAK
+
+
+def _device_f32(t, who, what, dims):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise _lib.CimHipError("cim_amd.prm_train.%s: CUDA/HIP tensor expected (no CPU fallback)" % who)
+    if t.dim() != dims or t.dtype != torch.float32:
+        raise ValueError("cim_amd.prm_train.%s: %s must be %d-dimensional float32, got %s %s" % (who, what, dims, tuple(t.shape), t.dtype))
+
+
+class StimulationState(object):
+    """What one peak_stimulation call left on the device: bitmap [B,C,ceil(H W / 32)] uint32 words (int32 storage), count,
+    status [B,C] int32, median [B,C] f32.  Nothing here is read by the training step."""
+
+    def __init__(self, shape, factor, device):
+        b, c, h, w = shape
+        self.shape, self.factor = (b, c, h, w), factor
+        self.up_shape = (h * factor, w * factor)
+        self.words = (self.up_shape[0] * self.up_shape[1] + 31) // 32
+        self.bitmap = torch.empty((b, c, self.words), dtype=torch.int32, device=device)
+        self.count = torch.empty((b, c), dtype=torch.int32, device=device)
+        self.status = torch.empty((b, c), dtype=torch.int32, device=device)
+        self.median = torch.empty((b, c), dtype=torch.float32, device=device)
+
+    def peak_map(self):
+        """The peak map [B,C,H,W] bool on the device."""
+        H, W = self.up_shape
+        bits = (self.bitmap[..., None] >> torch.arange(32, device=self.bitmap.device, dtype=torch.int32)) & 1
+        return bits.reshape(self.shape[0], self.shape[1], -1)[..., :H * W].reshape(self.shape[:2] + (H, W)).bool()
+
+    def peak_list(self):
+        """The reference's torch.nonzero(peak_map): [P,4] int64 = (image, class, y, x), row-major.  Reads the device."""
+        return torch.nonzero(self.peak_map())
+
+    def check(self):
+        """Raises ValueError naming the first (image, class) whose map had a NaN or no peak.  Reads the device."""
+        status = self.status.cpu().numpy()
+        for i, j in zip(*np.nonzero(status)):
+            why = "a NaN in it" if status[i, j] & STATUS_NAN else "no peak (every value -inf)"
+            raise ValueError("cim_amd.prm_train: the class response map of image %d, class %d has %s: its aggregation is NaN" % (i, j, why))
+        return self
+
+
+class PeakStimulationFunction(Function):
+    @staticmethod
+    def forward(ctx, crm, bias, factor, state):
+        b, c, h, w = state.shape
+        agg = torch.empty((b, c), dtype=torch.float32, device=crm.device)
+        _lib.call("cim_prmt_stim_forward", crm.data_ptr(), _lib.ptr(bias), b, c, h, w, factor, agg.data_ptr(), state.count.data_ptr(),
+                  state.median.data_ptr(), state.status.data_ptr(), state.bitmap.data_ptr(), _lib.stream_ptr())
+        ctx.state, ctx.has_bias = state, bias is not None
+        return agg
+
+    @staticmethod
+    def backward(ctx, grad_agg):
+        state = ctx.state
+        b, c, h, w = state.shape
+        grad_agg = grad_agg.contiguous()
+        dcrm = torch.empty(state.shape, dtype=torch.float32, device=grad_agg.device)
+        dbias = torch.empty(c, dtype=torch.float32, device=grad_agg.device) if ctx.has_bias and ctx.needs_input_grad[1] else None
+        _lib.call("cim_prmt_stim_backward", grad_agg.data_ptr(), state.count.data_ptr(), state.bitmap.data_ptr(), b, c, h, w, state.factor,
+                  dcrm.data_ptr(), _lib.ptr(dbias), _lib.stream_ptr())
+        return dcrm, dbias, None, None
+
+
+def peak_stimulation(crm, factor=8, bias=None):
+    """crm [B,C,h,w] fp32 on the device (+ bias [C], added before the up-sampling) -> (aggregation [B,C], state): the mean of the
+    peaks of each map up-sampled by `factor` (bilinear, align_corners=True; median filter, 3 x 3 window).  The aggregation carries
+    the gradient to crm and bias; one launch forward, one backward (two with a bias)."""
+    _device_f32(crm, "peak_stimulation", "crm", 4)
+    if bias is not None:
+        _device_f32(bias, "peak_stimulation", "bias", 1)
+        if bias.shape[0] != crm.shape[1]:
+            raise ValueError("cim_amd.prm_train.peak_stimulation: %d bias values for %d classes" % (bias.shape[0], crm.shape[1]))
+        bias = bias.contiguous()
+    f = int(factor)
+    b, c, h, w = (int(s) for s in crm.shape)
+    if f < 1 or min(b, c, h, w) < 1:
+        raise ValueError("cim_amd.prm_train.peak_stimulation: factor = %d on maps of shape %s" % (f, (b, c, h, w)))
+    if h * f * w * f > STIM_MAX_HW:
+        raise ValueError("cim_amd.prm_train.peak_stimulation: %d x %d up-sampled pixels, at most %d" % (h * f, w * f, STIM_MAX_HW))
+    state = StimulationState((b, c, h, w), f, crm.device)
+    return PeakStimulationFunction.apply(crm.contiguous(), bias, f, state), state
+
+
+class MsmLossFunction(Function):
+    @staticmethod
+    def forward(ctx, agg, target):
+        b, c = agg.shape
+        loss = torch.empty(1, dtype=torch.float32, device=agg.device)
+        dagg = torch.empty_like(agg)
+        _lib.call("cim_prmt_msm_loss", agg.data_ptr(), target.data_ptr(), b, c, loss.data_ptr(), dagg.data_ptr(), _lib.stream_ptr())
+        ctx.save_for_backward(dagg)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad):
+        dagg, = ctx.saved_tensors
+        return dagg * grad, None
+
+
+def multilabel_soft_margin_loss(aggregation, target):
+    """torch's F.multilabel_soft_margin_loss(aggregation, target) as ONE single-workgroup launch that also writes the gradient
+    (sigmoid(x) - t) / (B C): aggregation, target [B,C] fp32 on the device -> a scalar with a gradient to the aggregation."""
+    _device_f32(aggregation, "multilabel_soft_margin_loss", "aggregation", 2)
+    _device_f32(target, "multilabel_soft_margin_loss", "target", 2)
+    if aggregation.shape != target.shape or aggregation.numel() < 1:
+        raise ValueError("cim_amd.prm_train.multilabel_soft_margin_loss: aggregation %s against target %s" % (tuple(aggregation.shape), tuple(target.shape)))
+    return MsmLossFunction.apply(aggregation.contiguous(), target.contiguous())
+
+
+def freeze(model, at=2):
+    """requires_grad = False on the stem and on layer1 .. layer{at-1} of the PeakResponseMapping `model` (at in 2..5; 2 = the
+    stage up to which the detector's body freezes, ResNet.FREEZE_AT).  The stem is always frozen: its kernel is forward only."""
+    if at not in (2, 3, 4, 5):
+        raise ValueError("cim_amd.prm_train.freeze: at = %r, one of 2, 3, 4, 5 is needed" % (at,))
+    f = _features(model)
+    for i in range(0, 3 + at):               # features: conv1, bn1, relu, maxpool, layer1 (index 4) ..
+        for p in f[i].parameters():
+            p.requires_grad = False
+    return model
+
+
+def _features(model):
+    if not isinstance(model, _prm.PeakResponseMapping) or not isinstance(model[0], _prm.FC_ResNet):
+        raise TypeError("cim_amd.prm_train: a cim_amd.prm.PeakResponseMapping over a cim_amd.prm.FC_ResNet is expected")
+    return model[0].features
+
+
+_IDENTITY_BN = {}      # (device, classes) -> a BatchNorm2d that is y = x exactly (gamma 1, beta 0, mean 0, var 1, eps 0), not trained
+
+
+def _identity_bn(device, c):
+    key = (device, c)
+    if key not in _IDENTITY_BN:
+        bn = torch.nn.BatchNorm2d(c, eps=0.0).to(device).eval()
+        for p in bn.parameters():
+            p.requires_grad = False
+        _IDENTITY_BN[key] = bn
+    return _IDENTITY_BN[key]
+
+
+def class_response_maps(model, images):
+    """model[0] under the current grad mode: the stem (forward only), layer1..layer4 and the 1 x 1 classifier on the fused launches,
+    the classifier WITH autograd - its convolution bias folded into the identity BatchNorm's mean (ops/conv1x1.py), its weight
+    and bias gradients from the small-tile GEMM path."""
+    f = _features(model)
+    if any(p.requires_grad for i in range(4) for p in f[i].parameters()) and torch.is_grad_enabled():
+        raise ValueError("cim_amd.prm_train: the stem cannot train (conv7x7_bn_act is forward only): call prm_train.freeze(model) first")
+    x = max_pool2d(conv7x7_bn_act(images, f[0], f[1], relu=True), f[3])
+    for i in range(4, 8):
+        x = f[i](x)
+    conv = model[0].classifier[0]
+    return conv1x1_bn_act(x, conv, _identity_bn(x.device, conv.out_channels), relu=False)
+
+
+def aggregate(model, images):
+    """images [B,3,S,S'] normalised fp32 on the device -> (aggregation [B,C], state): class_response_maps, then peak_stimulation
+    at the model's sub_pixel_locating_factor."""
+    _device_f32(images, "aggregate", "images", 4)
+    return peak_stimulation(class_response_maps(model, images), int(model.sub_pixel_locating_factor))
+
+
+def loss(model, images, target):
+    """The PRM classification loss of a batch: `aggregate`, then `multilabel_soft_margin_loss` against target [B,C]."""
+    agg, _ = aggregate(model, images)
+    return multilabel_soft_margin_loss(agg, target)

@@ -540,6 +540,44 @@ int cim_prm_points(const float* crm, const float* bias, int B, int C, int h, int
                    const int32_t* desc_dev, float peak_threshold, float* median, int32_t* pair_counts, int32_t* points,
                    float* scores, int32_t* image_out, void* ws, void* stream);
 
+/* ------------------------------------------------------------------ PRM classification training head: peak stimulation and loss (ABI-16 addition)
+ * Replaces, for training the PRM classifier, what lib/prm/prm_model.py composes from F.upsample(align_corners=True), the
+ * median filter, lib/prm/prm_modules.py:9-51 (PeakStimulation forward and backward) and F.multilabel_soft_margin_loss: class
+ * response maps -> aggregated class scores -> loss, with the gradient back to the class response maps.  ALL B C maps are
+ * processed, one 256-thread workgroup each; the up-sampled map lives in LDS and is never written to memory.  Stateless and
+ * re-entrant on the caller's stream; no workspace; no float atomics; every sum in a fixed order.  Additive: cim_abi_version()
+ * stays 16.  Exactness contract, the summation orders and the stated differences from the reference: DESIGN.md 4.21.
+ * (The entries are named cim_prmt_*: "PRM training".)
+ *
+ * Refused before any launch (-1, cim_last_error() names the condition): B < 1, C < 1, h < 1, w < 1, factor < 1, an up-sampled
+ * map of more than CIM_PRM_STIM_MAX_HW pixels (factor h x factor w; it has to fit LDS twice per CU), B C beyond 2^24, a NULL
+ * pointer other than bias / dbias.
+ *
+ * cim_prmt_stim_forward: crm [B, C, h, w] f32 (+ bias [C] or NULL, added to every tap) -> per map, with H = factor h, W = factor w:
+ *   the up-sampled map (the arithmetic of cim_prm_upsample, bit for bit), its LOWER median, the peak test of cim_prm_peaks
+ *   (3 x 3 window, -inf padding, first maximum wins, value >= median),
+ *   bitmap [B, C, ceil(H W / 32)] uint32: bit (p & 31) of word p >> 5 is set for a peak at pixel p = y W + x (nothing is dropped),
+ *   count [B, C] int32 the number of peaks, median [B, C] f32,
+ *   agg [B, C] f32 = (sum of the peak values, in the order of DESIGN.md 4.21) / count,
+ *   status [B, C] int32 = 0, CIM_PRM_STATUS_NAN (a NaN in the up-sampled map) or CIM_PRM_STATUS_NO_PEAK (an up-sampled map of
+ *   -inf only): such a map has no peak, count 0, agg = the quiet NaN 0x7fc00000 (the reference's 0 / 0); with a NaN the median is
+ *   that NaN too.  (The up-sampling gives inf x 0 = NaN for an infinite tap, as ATen's does: a class response map of -inf
+ *   reports CIM_PRM_STATUS_NAN.)
+ *   One launch.
+ * cim_prmt_stim_backward: grad_agg [B, C] f32, count, bitmap (of the forward with the same B, C, h, w, factor) ->
+ *   dcrm [B, C, h, w] f32 = sum over the peaks q in row-major order of wy(q) wx(q) (grad_agg / count): the forward's own fp32
+ *   tap weights on the forward's own tap pixels, gathered per low-resolution pixel; all 0 for a map without a
+ *   peak.  dbias [C] f32 or NULL: the sum of dcrm over the map and the batch, in a second launch.
+ * cim_prmt_msm_loss: agg [B, C] f32, target [B, C] f32 in [0, 1] -> loss [1] f32 = torch's multilabel_soft_margin_loss (the mean
+ *   over images and classes of -(t logsigmoid(x) + (1 - t) logsigmoid(-x)), softplus form, finite for every finite x) and
+ *   dagg [B, C] f32 = (sigmoid(x) - t) / (B C), both written by ONE single-workgroup launch. */
+#define CIM_PRM_STIM_MAX_HW 16384
+int cim_prmt_stim_forward(const float* crm, const float* bias, int B, int C, int h, int w, int factor, float* agg, int32_t* count,
+                          float* median, int32_t* status, uint32_t* bitmap, void* stream);
+int cim_prmt_stim_backward(const float* grad_agg, const int32_t* count, const uint32_t* bitmap, int B, int C, int h, int w,
+                           int factor, float* dcrm, float* dbias, void* stream);
+int cim_prmt_msm_loss(const float* agg, const float* target, int B, int C, float* loss, float* dagg, void* stream);
+
 /* ------------------------------------------------------------------ Pillow's antialiased resize: raw RGB images to PRM inputs (ABI-16 addition)
  * Replaces the host call Image.resize((448, 448), Image.BILINEAR) in front of the PRM (tools/pre/AGPL_label_assign.py through
  * prm_configs.open_transform: transforms.Resize([448, 448]), ToTensor, Normalize) for a BATCH of images of differing sizes.
