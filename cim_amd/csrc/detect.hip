@@ -27,6 +27,7 @@
 // helpers, the block scan and the limit's radix select with the kernels above.
 #pragma clang fp contract(off)                      // (x2 - x1 + 1) * ... and iarea + area - w*h: no fused multiply-adds
 #include "common.h"
+#include "wave_block.h"
 #include "../../include/cim_hip.h"
 #include <limits.h>
 #include <algorithm>
@@ -35,35 +36,7 @@ namespace {
 
 constexpr int kMaxN = CIM_DETECT_MAX_N;
 
-// the greedy pass compares scores as unsigned integers: IEEE order for every non-NaN float, -0 == +0 (NumPy's sort)
-__device__ __forceinline__ uint32_t orderable(float f) {
-    if (f == 0.0f) f = 0.0f;
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-template <typename T>
-__device__ T block_exclusive_scan(T v, T* part, T* total) {              // 1024 lanes; returns the exclusive prefix
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    T incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T x = __shfl_up(incl, o);
-        if (lane >= o) incl += x;
-    }
-    __syncthreads();                                                     // (part[] of the previous scan has been read)
-    if (lane == 63) part[wave] = incl;
-    __syncthreads();
-    T woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-        const T p = part[w];
-        tot += p;
-        woff += (w < wave) ? p : 0;
-    }
-    *total = tot;
-    return woff + incl - v;
-}
+// (the greedy pass compares scores as unsigned integers: orderable() of wave_block.h, which also holds the block scan)
 
 // cython_nms.pyx:28-32 - the ternaries, not fmaxf / fminf (they differ on NaN)
 __device__ __forceinline__ float pyx_max(float a, float b) { return a >= b ? a : b; }

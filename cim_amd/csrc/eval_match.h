@@ -4,6 +4,7 @@
 // has internal linkage.
 #pragma once
 #include "common.h"
+#include "wave_block.h"                             // orderable(): descending score as an ascending unsigned key, ~orderable(s)
 #include "../../include/cim_hip.h"
 
 namespace {
@@ -12,13 +13,6 @@ typedef unsigned long long u64;
 
 constexpr int kMaxGt = CIM_SEGM_MAX_GT;
 constexpr int kMaxDt = CIM_DETECT_MAX_N;
-
-// descending score as an ascending unsigned key: IEEE order, -0 == +0 (NumPy's argsort of -score)
-__device__ __forceinline__ uint32_t orderable(float f) {
-    if (f == 0.0f) f = 0.0f;
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // ---- per-image evaluation ---------------------------------------------------------------------------------------------------
 // meta (int32): groups [n_groups][8] = (det_start, n_det, gt_start, n_gt, nd_keep, rec_off, pair_off, 0), then det_list [n_dl]

@@ -11,6 +11,7 @@
 //   fp32, log via logf; every score is clamped to [1e-6, 1-1e-6] before a log exactly like the
 //   reference, with the clamp's pass-through gradient (inclusive bounds).
 #include "common.h"
+#include "wave_block.h"                             // wave_argmax: ties -> lower index (first maximum)
 #include "../../include/cim_hip.h"
 #include <limits.h>
 
@@ -56,16 +57,6 @@ __device__ void block_sum4(float& v0, float& v1, float& v2, float& v3, float* bu
     float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
     for (int w = 0; w < NT / 64; ++w) { s0 += buf[w * 4 + 0]; s1 += buf[w * 4 + 1]; s2 += buf[w * 4 + 2]; s3 += buf[w * 4 + 3]; }
     v0 = s0; v1 = s1; v2 = s2; v3 = s3;
-}
-
-// (value, index) max over the 64 lanes; ties -> lower index (first maximum)
-__device__ __forceinline__ void wave_argmax(float& v, int& i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o);
-        const int oi = __shfl_xor(i, o);
-        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-    }
 }
 
 // lanes per row of the column passes: the smallest power of two >= C1 (1024: one wave per column instead)

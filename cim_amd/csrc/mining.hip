@@ -18,6 +18,7 @@
 // No library state: the words through which the workgroups of the mining launch meet (arrival counters, list lengths) live in a
 // CALLER-owned scratch (cim_mining_sync_bytes(), zero-filled once at allocation) that every call leaves zeroed again.
 #include "common.h"
+#include "wave_block.h"
 #include "../../include/cim_hip.h"
 #include <limits.h>
 
@@ -88,35 +89,6 @@ __global__ __launch_bounds__(256) void transpose_f16_kernel(const uint16_t* __re
     }
 }
 
-// ---------------------------------------------------------------- heads.py:354-380
-__device__ __forceinline__ uint32_t orderable(float f) {
-    if (f == 0.0f) f = 0.0f;  // -0 == +0 for the comparison sort
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ int block_exclusive_scan(int v, int* part, int* total) {      // 1024 lanes; returns the exclusive prefix
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;       // wave scans in registers, 16 wave totals through LDS:
-    int incl = v;                                                        // two barriers instead of the 20 of an all-LDS scan
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int x = __shfl_up(incl, o);
-        if (lane >= o) incl += x;
-    }
-    __syncthreads();                                                     // (part[] of the previous scan has been read)
-    if (lane == 63) part[wave] = incl;
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-        const int p = part[w];
-        tot += p;
-        woff += (w < wave) ? p : 0;
-    }
-    *total = tot;
-    return woff + incl - v;
-}
-
 // The words the workgroups of the mining launch meet through (caller-owned, zero between calls).
 struct MiningSync {
     unsigned arrive[CIM_MAX_LAYERS];                 // (class, layer) workgroups of a layer that finished their seed phase
@@ -133,6 +105,64 @@ struct SeedLayout {
     int total;
 };
 
+// ... and the typed pointers into it that the stages of the seed phase share
+struct SeedView {
+    unsigned* hist;                                  // the select's four 256-bin histograms
+    unsigned long long* cand;                        // [K] the select's survivors, unranked
+    unsigned long long* sup;                         // [K][KW] suppression bit-matrix
+    int32_t* kidx;                                   // [K] top-K proposals in rank order
+    int32_t* sseed;                                  // [K] seeds
+    float* sdet;                                     // [N] the layer's detector column (det_lds)
+    uint8_t* sflag;                                  // [N] not-huge flags (det_lds)
+    uint16_t* row;                                   // 16 wave-private map rows of row_halves entries (row_lds)
+};
+__device__ __forceinline__ SeedView seed_view(const SeedLayout& lay, unsigned char* smem) {
+    SeedView v;
+    v.hist = reinterpret_cast<unsigned*>(smem);
+    v.cand = reinterpret_cast<unsigned long long*>(smem + lay.off_cand);
+    v.sup = reinterpret_cast<unsigned long long*>(smem + lay.off_sup);
+    v.kidx = reinterpret_cast<int32_t*>(smem + lay.off_kidx);
+    v.sseed = reinterpret_cast<int32_t*>(smem + lay.off_seed);
+    v.sdet = reinterpret_cast<float*>(smem + lay.off_det);
+    v.sflag = smem + lay.off_flag;
+    v.row = reinterpret_cast<uint16_t*>(smem + lay.off_row);
+    return v;
+}
+
+__device__ __forceinline__ float det_score(const cim_mining_layer& L, int c, int i) {
+    return L.det[(size_t)i * L.det_ld + L.det_off + c * L.det_cs];
+}
+
+// One round trip for everything the seed phase reads per proposal: lane t owns the proposals [t Rk, t Rk + Rk) - their seed
+// scores stay in registers (sc[]: the select's keys), their detector scores and flags go to LDS for the containment step (`stage`)
+template <int MAXR>
+__device__ __forceinline__ void seed_load(const cim_mining_layer& L, const uint8_t* __restrict__ flag, bool stage,
+                                          const SeedView& v, int N, int c, float (&sc)[MAXR]) {
+    const int tid = threadIdx.x, Rk = (N + 1023) >> 10;
+    const float* __restrict__ score = L.seed_score;
+    const int score_ld = L.seed_ld, col = L.seed_off + c;
+    float dv[MAXR];
+    uint8_t fv[MAXR];
+#pragma unroll
+    for (int r = 0; r < MAXR; ++r) {
+        const int i = tid * Rk + r;
+        const bool in = r < Rk && i < N;
+        sc[r] = in ? score[(size_t)i * score_ld + col] : 0.0f;
+        dv[r] = (in && stage) ? det_score(L, c, i) : 0.0f;
+        fv[r] = (in && stage) ? flag[i] : (uint8_t)0;
+    }
+    if (stage) {
+#pragma unroll
+        for (int r = 0; r < MAXR; ++r) {
+            const int i = tid * Rk + r;
+            if (r < Rk && i < N) {
+                v.sdet[i] = dv[r];
+                v.sflag[i] = fv[r];
+            }
+        }
+    }
+}
+
 // ================================================================== the mining launch, phase 1: seeds of one (class, layer)
 // Top-K by RADIX SELECT (the reference takes argsort(descending)[:K], heads.py:354: only K = ceil(0.1 N) of the N keys are
 // wanted in order): four 8-bit histogram passes over the orderable score bits find the K-th largest value T and how many
@@ -141,11 +171,9 @@ struct SeedLayout {
 // barrier per pass: the histograms of all four passes are cleared up front and every wave scans a pass's 256 bins for
 // itself.  Round 4 sorted all N keys (bitonic, 55 exchange stages): 12.5 of the kernel's 37 us.
 template <int MAXR>
-__device__ __forceinline__ void seed_topk_select(const float (&sc)[MAXR], int N, int K,
-                                                 unsigned* __restrict__ hist, unsigned long long* __restrict__ cand,
-                                                 int32_t* __restrict__ kidx, int32_t* __restrict__ topk_out, int* s_misc,
-                                                 int* s_part, int tid) {
-    const int lane = tid & 63;
+__device__ __forceinline__ void topk_threshold_and_compact(const float (&sc)[MAXR], int N, int K, unsigned* __restrict__ hist,
+                                                           unsigned long long* __restrict__ cand, int* s_misc, int* s_part) {
+    const int tid = threadIdx.x, lane = tid & 63;
     const int Rk = (N + 1023) >> 10;                 // keys per lane: lane t owns the proposals [t Rk, t Rk + Rk) (scores in sc[])
     unsigned key[MAXR];
     unsigned valid = 0;
@@ -224,7 +252,12 @@ __device__ __forceinline__ void seed_topk_select(const float (&sc)[MAXR], int N,
             ((unsigned long long)(~key[r]) << 32) | (unsigned)(tid * Rk + r);     // (descending score, ascending index)
     }
     __syncthreads();
-    // rank of each survivor among the K: G lanes per survivor count a share of the list each
+}
+
+// rank of each survivor among the K: G lanes per survivor count a share of the list each
+__device__ __forceinline__ void topk_rank(int K, const unsigned long long* __restrict__ cand, int32_t* __restrict__ kidx,
+                                          int32_t* __restrict__ topk_out) {
+    const int tid = threadIdx.x;
     int Kp = 1;
     while (Kp < K) Kp <<= 1;
     int G = 1024 / Kp;
@@ -245,301 +278,287 @@ __device__ __forceinline__ void seed_topk_select(const float (&sc)[MAXR], int N,
     __syncthreads();
 }
 
+template <int MAXR>
+__device__ __forceinline__ void seed_topk_select(const float (&sc)[MAXR], int N, int K, const SeedView& v, int32_t* topk_out,
+                                                 int* s_misc, int* s_part) {
+    topk_threshold_and_compact<MAXR>(sc, N, K, v.hist, v.cand, s_misc, s_part);
+    topk_rank(K, v.cand, v.kidx, topk_out);
+}
+
+// Suppression bit-matrix over the K x K gathered sub-block of the mask-IoU map:
+// bit (i, j) set <=> NOT (iou[idx_i, idx_j] < nms_thr)   (heads.py:250-254, fp16 compare).  Two forms:
+//
+// ROW STREAMING: one wave per candidate row reads the candidate's WHOLE row of the map in 16-byte pieces (coalesced; the K
+// wanted columns - a tenth of the row, scattered - touch nearly every 64-byte line of it anyway: gathering them one by one
+// moved 3x the bytes through this CU's L1, 24 of the phase's 52 us at 2000 proposals), parks it in a wave-private LDS
+// row and picks its K columns from there (one 2-byte LDS read per candidate and 64-candidate word, a ballot per word).
+// Rows start at any 2-byte offset: the pieces are loaded from the 16-byte boundary below through a buffer resource over
+// the map (reads behind its end return 0), the columns are shifted accordingly.  The next row's pieces are in flight
+// while this one is picked apart.
+__device__ __forceinline__ void suppression_from_rows(const uint16_t* __restrict__ iou, int N, int K, float nms_thr, int row_halves,
+                                                      const SeedView& v) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, KW = (K + 63) >> 6;
+    const rsrc_t R = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(iou), 0, (int)(2u * (unsigned)N * (unsigned)N), 0x00020000);
+    uint16_t* __restrict__ myrow = v.row + (size_t)wave * row_halves;
+    const int nch = row_halves >> 3;                                     // 16-byte pieces per row (<= 4 per lane)
+    int cj[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int j = w * 64 + lane;
+        cj[w] = (w < KW && j < K) ? v.kidx[j] : -1;
+    }
+    u32x4 cur[4], nxt[4];
+    int sh_c = 0, sh_n = 0;
+    auto issue = [&](int i, u32x4 (&buf)[4], int& shift) {
+        const unsigned b = 2u * (unsigned)v.kidx[i] * (unsigned)N;
+        shift = (int)((b & 15u) >> 1);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int ch = lane + 64 * k;
+            buf[k] = ch < nch ? __builtin_amdgcn_raw_buffer_load_b128(R, (b & ~15u) + 16u * (unsigned)ch, 0, 0) : u32x4{0, 0, 0, 0};
+        }
+    };
+    int i = wave;
+    if (i < K) issue(i, cur, sh_c);
+    for (; i < K; i += 16) {
+        if (i + 16 < K) issue(i + 16, nxt, sh_n);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int ch = lane + 64 * k;
+            if (ch < nch) *reinterpret_cast<u32x4*>(myrow + ch * 8) = cur[k];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");           // (LDS operations of a wave execute in order: no wait needed,
+        __builtin_amdgcn_wave_barrier();                                 // only the compiler must keep the writes above the reads)
+        const int w_lo = i >> 6;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            if (w >= KW) break;
+            unsigned long long word = 0ull;
+            if (w >= w_lo) {                                             // (the greedy scan only looks at candidates behind row i)
+                const uint16_t x = cj[w] >= 0 ? myrow[cj[w] + sh_c] : (uint16_t)0;
+                word = __ballot(cj[w] >= 0 && !(h2f(x) < nms_thr));
+            }
+            if (lane == 0) v.sup[(size_t)i * KW + w] = word;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int k = 0; k < 4; ++k) cur[k] = nxt[k];
+        sh_c = sh_n;
+    }
+}
+
+// GATHERS (rows too long for the streaming form, or more than four words per row): one 2-byte load per pair
+__device__ __forceinline__ void suppression_from_gathers(const uint16_t* __restrict__ iou, int N, int K, float nms_thr,
+                                                         const SeedView& v) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, KW = (K + 63) >> 6;
+    constexpr int GU = 13;                                               // gathers in flight per wave (latency-bound: the map is
+    for (int t0 = wave; t0 < K * KW; t0 += 16 * GU) {                    // L2-resident, each gather a round trip; K = 100: one round)
+        uint16_t x[GU];
+#pragma unroll
+        for (int u = 0; u < GU; ++u) {
+            const int t = t0 + 16 * u;
+            const int i = t / KW, w = t % KW, j = w * 64 + lane;
+            // (the greedy scan only looks at candidates behind row i: the words below its own 64-block stay zero)
+            x[u] = (t < K * KW && j < K && w >= (i >> 6)) ? iou[(size_t)v.kidx[i] * N + v.kidx[j]] : (uint16_t)0;
+        }
+#pragma unroll
+        for (int u = 0; u < GU; ++u) {
+            const int t = t0 + 16 * u;
+            if (t >= K * KW) break;
+            const int i = t / KW, w = t % KW, j = w * 64 + lane;
+            const unsigned long long word = __ballot(j < K && w >= (i >> 6) && !(h2f(x[u]) < nms_thr));
+            if (lane == 0) v.sup[t] = word;
+        }
+    }
+}
+
+// Greedy scan in score order by ONE wave; lane w owns word w of the "removed" set.  The scan is sequential in the
+// KEPT candidates, 64 candidates at a time: the block's own 64 x 64 suppression bits sit one row per lane in
+// registers, the next kept candidate is a count-trailing-zeros on the scalar "removed" word and its row a readlane (no LDS
+// on the serial chain); the rows of the kept candidates are then OR-ed into the later words with independent LDS reads.
+// Writes the seeds (global and LDS) and their number (*n_seeds_out, s_misc[3]).
+__device__ __forceinline__ void greedy_seed_scan(int K, const SeedView& v, int32_t* __restrict__ seeds, int32_t* n_seeds_out,
+                                                 int* s_misc) {
+    const int lane = threadIdx.x & 63, KW = (K + 63) >> 6;
+    int cnt = 0;
+    unsigned long long removed = 0ull;  // lane l holds word l (l < KW <= 64)
+    for (int i0 = 0; i0 < K; i0 += 64) {
+        const int nb = min(64, K - i0), wb = i0 >> 6;
+        const unsigned long long rowblk = lane < nb ? v.sup[(size_t)(i0 + lane) * KW + wb] : 0ull;
+        const unsigned rlo = (unsigned)rowblk, rhi = (unsigned)(rowblk >> 32);
+        // rem / kept live in SGPRs (readfirstlane): the 64 steps are scalar shifts and selects, the row reads
+        // (v_readlane, independent of rem) run ahead of them
+        const unsigned long long r0 = __shfl(removed, wb);
+        unsigned long long rem = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(r0 >> 32)) << 32) |
+                                 (unsigned)__builtin_amdgcn_readfirstlane((int)r0);
+        unsigned long long kept = 0ull;
+        // walk the ALIVE candidates only: the next one is the lowest clear bit of `rem` (a kept candidate's row always has
+        // its own bit set - iou(i, i) is 1 or NaN, neither is < nms_thr - and is cleared explicitly as well)
+        const unsigned long long inblk = nb == 64 ? ~0ull : ((1ull << nb) - 1ull);
+        unsigned long long alive = ~rem & inblk;
+        while (alive) {
+            const int t = __builtin_amdgcn_readfirstlane(__builtin_ctzll(alive));
+            const unsigned long long row = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(rhi, t) << 32) |
+                                           (unsigned)__builtin_amdgcn_readlane(rlo, t);          // (readlane returns int)
+            kept |= 1ull << t;
+            rem |= row | (1ull << t);
+            alive = ~rem & inblk & (t == 63 ? 0ull : (~0ull << (t + 1)));
+        }
+        if ((kept >> lane) & 1ull) {
+            const int at = cnt + __popcll(kept & ((1ull << lane) - 1ull));
+            const int32_t id = v.kidx[i0 + lane];
+            seeds[at] = id;
+            v.sseed[at] = id;
+        }
+        cnt += __popcll(kept);
+        if (lane < KW)
+            for (unsigned long long k = kept; k;) {                      // four independent LDS reads per round (a repeated row is harmless)
+                const int t0 = __builtin_ctzll(k);
+                k &= k - 1ull;
+                const int t1 = k ? __builtin_ctzll(k) : t0;
+                k &= k - 1ull;
+                const int t2 = k ? __builtin_ctzll(k) : t0;
+                k &= k - 1ull;
+                const int t3 = k ? __builtin_ctzll(k) : t0;
+                k &= k - 1ull;
+                removed |= (v.sup[(size_t)(i0 + t0) * KW + lane] | v.sup[(size_t)(i0 + t1) * KW + lane]) |
+                           (v.sup[(size_t)(i0 + t2) * KW + lane] | v.sup[(size_t)(i0 + t3) * KW + lane]);
+            }
+    }
+    for (int r = cnt + lane; r < K; r += 64) seeds[r] = -1;
+    if (lane == 0) {
+        *n_seeds_out = cnt;
+        s_misc[3] = cnt;
+    }
+}
+
+// Containment arg-max (heads.py:386-395): res[s] = the best-det proposal among {i : asy[i, seed_s] > con_thr and not huge(i)},
+// first index on equal detector scores; one wave per seed walks the seed's column of the containment map.
+//
+// Over the TRANSPOSED map: two seeds per wave and round, a lane takes 8 consecutive proposals per 512-proposal chunk: one 16-byte
+// load per seed and chunk from the seed's row of the transposed map (rows padded to 8 entries: 16-byte aligned), all of a
+// round's loads in flight before the first compare.
+__device__ __forceinline__ void containment_argmax_transposed(const cim_mining_args& a, const cim_mining_layer& L, int det_lds,
+                                                              const SeedView& v, const uint8_t* __restrict__ flag, int c,
+                                                              int n_seeds, int32_t* __restrict__ res) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, N = a.N, K = a.K;
+    const float thr = L.con_thr;
+    const int ldt = (N + 7) & ~7;
+    for (int s0 = wave * 2; s0 < K; s0 += 32) {
+        const bool on0 = s0 < n_seeds, on1 = s0 + 1 < n_seeds;           // (uniform per wave)
+        if (!on0) {
+            if (lane == 0) res[s0] = -1;
+            if (lane == 1 && s0 + 1 < K) res[s0 + 1] = -1;
+            continue;
+        }
+        const uint4* __restrict__ row0 = reinterpret_cast<const uint4*>(a.asy_t + (size_t)v.sseed[s0] * ldt);
+        const uint4* __restrict__ row1 = reinterpret_cast<const uint4*>(a.asy_t + (size_t)v.sseed[on1 ? s0 + 1 : s0] * ldt);
+        float best0 = -INFINITY, best1 = -INFINITY;
+        int bi0 = INT_MAX, bi1 = INT_MAX, any0 = 0, any1 = 0;
+        for (int i0 = lane * 8; i0 < ldt; i0 += 512) {
+            const uint4 v0 = row0[i0 >> 3], v1 = row1[i0 >> 3];
+            float d[8];
+            unsigned fl = 0;
+            if (det_lds) {
+                const float4 da = *reinterpret_cast<const float4*>(v.sdet + i0), db = *reinterpret_cast<const float4*>(v.sdet + i0 + 4);
+                const uint2 fb = *reinterpret_cast<const uint2*>(v.sflag + i0);
+                d[0] = da.x; d[1] = da.y; d[2] = da.z; d[3] = da.w; d[4] = db.x; d[5] = db.y; d[6] = db.z; d[7] = db.w;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) fl |= ((((e < 4 ? fb.x : fb.y) >> (8 * (e & 3))) & 0xffu) ? 1u : 0u) << e;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const int i = i0 + e;
+                    d[e] = i < N ? det_score(L, c, i) : 0.0f;
+                    fl |= (i < N && flag[i] ? 1u : 0u) << e;
+                }
+            }
+            const unsigned w0[4] = {v0.x, v0.y, v0.z, v0.w}, w1[4] = {v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int i = i0 + e;
+                const bool in = i < N && ((fl >> e) & 1u);
+                const bool c0 = in && h2f((uint16_t)(w0[e >> 1] >> (16 * (e & 1)))) > thr;
+                const bool c1 = in && h2f((uint16_t)(w1[e >> 1] >> (16 * (e & 1)))) > thr;
+                any0 |= c0;
+                any1 |= c1;
+                const float x0 = c0 ? d[e] : 0.0f, x1 = c1 ? d[e] : 0.0f;            // heads.py:393
+                if (i < N && x0 > best0) { best0 = x0; bi0 = i; }                     // ascending i per lane: strict '>' keeps the first maximum
+                if (i < N && x1 > best1) { best1 = x1; bi1 = i; }
+            }
+        }
+        wave_argmax(best0, bi0);
+        wave_argmax(best1, bi1);
+        any0 = __any(any0);
+        any1 = __any(any1);
+        if (lane == 0) res[s0] = any0 ? bi0 : -1;
+        if (lane == 1 && s0 + 1 < K) res[s0 + 1] = (on1 && any1) ? bi1 : -1;
+    }
+}
+
+// No transposed copy: strided reads of the map's column, one seed per wave and round
+__device__ __forceinline__ void containment_argmax_strided(const cim_mining_args& a, const cim_mining_layer& L, const SeedView& v,
+                                                           const uint8_t* __restrict__ flag, int c, int n_seeds,
+                                                           int32_t* __restrict__ res) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, N = a.N, K = a.K;
+    const float thr = L.con_thr;
+    for (int s = wave; s < K; s += 16) {
+        if (s >= n_seeds) {
+            if (lane == 0) res[s] = -1;
+            continue;
+        }
+        const int seed = v.sseed[s];
+        float best = -INFINITY;
+        int besti = INT_MAX;
+        int any = 0;
+#pragma unroll 4
+        for (int i = lane; i < N; i += 64) {
+            const bool cond = (h2f(a.asy[(size_t)i * N + seed]) > thr) && flag[i];
+            any |= cond;
+            const float x = cond ? det_score(L, c, i) : 0.0f;
+            if (x > best) {
+                best = x;
+                besti = i;
+            }
+        }
+        wave_argmax(best, besti);
+        any = __any(any);
+        if (lane == 0) res[s] = any ? besti : -1;
+    }
+}
+
 // Seeds of (class c, layer l): top-K select, K x K suppression bit-matrix, greedy scan, and - CIM layers - the containment
-// arg-max of every seed (heads.py:386-395; round 4: a launch of its own, one workgroup per seed column): one wave per seed
-// walks the seed's column of the containment map - a contiguous row of the transposed copy - against the layer's detector
-// column, first-index arg-max.
+// arg-max of every seed (round 4: a launch of its own, one workgroup per seed column).
 __device__ __forceinline__ void seed_phase(const cim_mining_args& a, const SeedLayout& lay, unsigned char* smem, int* s_misc,
                                            int* s_part, int c, int l) {
     const cim_mining_layer& L = a.layer[l];
-    const int tid = threadIdx.x, N = a.N, K = a.K;
-    const int wave = tid >> 6, lane = tid & 63;
-    const int KW = (K + 63) >> 6;
-    unsigned* hist = reinterpret_cast<unsigned*>(smem);
-    unsigned long long* cand = reinterpret_cast<unsigned long long*>(smem + lay.off_cand);
-    unsigned long long* sup = reinterpret_cast<unsigned long long*>(smem + lay.off_sup);
-    int32_t* kidx = reinterpret_cast<int32_t*>(smem + lay.off_kidx);
-    int32_t* sseed = reinterpret_cast<int32_t*>(smem + lay.off_seed);
-    float* sdet = reinterpret_cast<float*>(smem + lay.off_det);
-    uint8_t* sflag = smem + lay.off_flag;
-    int32_t* __restrict__ topk_out = L.topk + (size_t)c * K;
+    const int N = a.N, K = a.K, wave = threadIdx.x >> 6;
+    const SeedView v = seed_view(lay, smem);
+    int32_t* __restrict__ topk_out = L.topk + (size_t)c * K;             // (this workgroup's slices, addressed once up front)
     int32_t* __restrict__ seeds = L.seeds + (size_t)c * K;
     [[maybe_unused]] const int wg_act = (int)(l * 2 + (c & 1));          // (debug stamps only)
     MCLK(0, wg_act, 0);
     const uint8_t* __restrict__ flag = L.using_cim ? a.flags + (size_t)L.flag_slot * N : nullptr;
-    // ONE round trip for everything this phase reads per proposal: lane t owns the proposals [t Rk, t Rk + Rk) - their seed
-    // scores stay in registers (the select's keys), their detector scores and flags go to LDS for the containment step
     constexpr int MAXR = 8;
-    const int Rk = (N + 1023) >> 10;
     float sc[MAXR];
-    {
-        const float* __restrict__ score = L.seed_score;
-        const int score_ld = L.seed_ld, col = L.seed_off + c;
-        const bool stage = L.using_cim && lay.det_lds;
-        float dv[MAXR];
-        uint8_t fv[MAXR];
-#pragma unroll
-        for (int r = 0; r < MAXR; ++r) {
-            const int i = tid * Rk + r;
-            const bool in = r < Rk && i < N;
-            sc[r] = in ? score[(size_t)i * score_ld + col] : 0.0f;
-            dv[r] = (in && stage) ? L.det[(size_t)i * L.det_ld + L.det_off + c * L.det_cs] : 0.0f;
-            fv[r] = (in && stage) ? flag[i] : (uint8_t)0;
-        }
-        if (stage) {
-#pragma unroll
-            for (int r = 0; r < MAXR; ++r) {
-                const int i = tid * Rk + r;
-                if (r < Rk && i < N) {
-                    sdet[i] = dv[r];
-                    sflag[i] = fv[r];
-                }
-            }
-        }
-    }
+    seed_load<MAXR>(L, flag, L.using_cim && lay.det_lds, v, N, c, sc);
     // key = (descending score, ascending index): a total order -> the stable descending argsort of heads.py:354 (App. B item 4)
-    seed_topk_select<MAXR>(sc, N, K, hist, cand, kidx, topk_out, s_misc, s_part, tid);
+    seed_topk_select<MAXR>(sc, N, K, v, topk_out, s_misc, s_part);
     MCLK(0, wg_act, 1);
-    // Suppression bit-matrix over the K x K gathered sub-block of the mask-IoU map:
-    // bit (i, j) set <=> NOT (iou[idx_i, idx_j] < nms_thr)   (heads.py:250-254, fp16 compare).
     const float nms_thr = L.nms_thr;
-    if (lay.row_lds) {
-        // ROW STREAMING: one wave per candidate row reads the candidate's WHOLE row of the map in 16-byte pieces (coalesced; the K
-        // wanted columns - a tenth of the row, scattered - touch nearly every 64-byte line of it anyway: gathering them one by one
-        // moved 3x the bytes through this CU's L1, 24 of the phase's 52 us at 2000 proposals), parks it in a wave-private LDS
-        // row and picks its K columns from there (one 2-byte LDS read per candidate and 64-candidate word, a ballot per word).
-        // Rows start at any 2-byte offset: the pieces are loaded from the 16-byte boundary below through a buffer resource over
-        // the map (reads behind its end return 0), the columns are shifted accordingly.  The next row's pieces are in flight
-        // while this one is picked apart.
-        const rsrc_t R = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.iou), 0, (int)(2u * (unsigned)N * (unsigned)N), 0x00020000);
-        uint16_t* __restrict__ myrow = reinterpret_cast<uint16_t*>(smem + lay.off_row) + (size_t)wave * lay.row_halves;
-        const int nch = lay.row_halves >> 3;                             // 16-byte pieces per row (<= 4 per lane)
-        int cj[4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const int j = w * 64 + lane;
-            cj[w] = (w < KW && j < K) ? kidx[j] : -1;
-        }
-        u32x4 cur[4], nxt[4];
-        int sh_c = 0, sh_n = 0;
-        auto issue = [&](int i, u32x4 (&buf)[4], int& shift) {
-            const unsigned b = 2u * (unsigned)kidx[i] * (unsigned)N;
-            shift = (int)((b & 15u) >> 1);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int ch = lane + 64 * k;
-                buf[k] = ch < nch ? __builtin_amdgcn_raw_buffer_load_b128(R, (b & ~15u) + 16u * (unsigned)ch, 0, 0) : u32x4{0, 0, 0, 0};
-            }
-        };
-        int i = wave;
-        if (i < K) issue(i, cur, sh_c);
-        for (; i < K; i += 16) {
-            if (i + 16 < K) issue(i + 16, nxt, sh_n);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int ch = lane + 64 * k;
-                if (ch < nch) *reinterpret_cast<u32x4*>(myrow + ch * 8) = cur[k];
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");       // (LDS operations of a wave execute in order: no wait needed,
-            __builtin_amdgcn_wave_barrier();                             // only the compiler must keep the writes above the reads)
-            const int w_lo = i >> 6;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                if (w >= KW) break;
-                unsigned long long word = 0ull;
-                if (w >= w_lo) {                                         // (the greedy scan only looks at candidates behind row i)
-                    const uint16_t v = cj[w] >= 0 ? myrow[cj[w] + sh_c] : (uint16_t)0;
-                    word = __ballot(cj[w] >= 0 && !(h2f(v) < nms_thr));
-                }
-                if (lane == 0) sup[(size_t)i * KW + w] = word;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int k = 0; k < 4; ++k) cur[k] = nxt[k];
-            sh_c = sh_n;
-        }
-    } else {
-        constexpr int GU = 13;                                               // gathers in flight per wave (latency-bound: the map is
-        for (int t0 = wave; t0 < K * KW; t0 += 16 * GU) {                    // L2-resident, each gather a round trip; K = 100: one round)
-            uint16_t v[GU];
-    #pragma unroll
-            for (int u = 0; u < GU; ++u) {
-                const int t = t0 + 16 * u;
-                const int i = t / KW, w = t % KW, j = w * 64 + lane;
-                // (the greedy scan only looks at candidates behind row i: the words below its own 64-block stay zero)
-                v[u] = (t < K * KW && j < K && w >= (i >> 6)) ? a.iou[(size_t)kidx[i] * N + kidx[j]] : (uint16_t)0;
-            }
-    #pragma unroll
-            for (int u = 0; u < GU; ++u) {
-                const int t = t0 + 16 * u;
-                if (t >= K * KW) break;
-                const int i = t / KW, w = t % KW, j = w * 64 + lane;
-                const unsigned long long word = __ballot(j < K && w >= (i >> 6) && !(h2f(v[u]) < nms_thr));
-                if (lane == 0) sup[t] = word;
-            }
-        }
-    }
+    if (lay.row_lds) suppression_from_rows(a.iou, N, K, nms_thr, lay.row_halves, v);
+    else suppression_from_gathers(a.iou, N, K, nms_thr, v);
     __syncthreads();
     MCLK(0, wg_act, 2);
-
-    // Greedy scan in score order by one wave; lane w owns word w of the "removed" set.  The scan is sequential in the
-    // KEPT candidates, 64 candidates at a time: the block's own 64 x 64 suppression bits sit one row per lane in
-    // registers, the next kept candidate is a count-trailing-zeros on the scalar "removed" word and its row a readlane (no LDS
-    // on the serial chain); the rows of the kept candidates are then OR-ed into the later words with independent LDS reads.
-    if (wave == 0) {
-        int cnt = 0;
-        unsigned long long removed = 0ull;  // lane l holds word l (l < KW <= 64)
-        for (int i0 = 0; i0 < K; i0 += 64) {
-            const int nb = min(64, K - i0), wb = i0 >> 6;
-            const unsigned long long rowblk = lane < nb ? sup[(size_t)(i0 + lane) * KW + wb] : 0ull;
-            const unsigned rlo = (unsigned)rowblk, rhi = (unsigned)(rowblk >> 32);
-            // rem / kept live in SGPRs (readfirstlane): the 64 steps are scalar shifts and selects, the row reads
-            // (v_readlane, independent of rem) run ahead of them
-            const unsigned long long r0 = __shfl(removed, wb);
-            unsigned long long rem = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(r0 >> 32)) << 32) |
-                                     (unsigned)__builtin_amdgcn_readfirstlane((int)r0);
-            unsigned long long kept = 0ull;
-            // walk the ALIVE candidates only: the next one is the lowest clear bit of `rem` (a kept candidate's row always has
-            // its own bit set - iou(i, i) is 1 or NaN, neither is < nms_thr - and is cleared explicitly as well)
-            const unsigned long long inblk = nb == 64 ? ~0ull : ((1ull << nb) - 1ull);
-            unsigned long long alive = ~rem & inblk;
-            while (alive) {
-                const int t = __builtin_amdgcn_readfirstlane(__builtin_ctzll(alive));
-                const unsigned long long row = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(rhi, t) << 32) |
-                                               (unsigned)__builtin_amdgcn_readlane(rlo, t);          // (readlane returns int)
-                kept |= 1ull << t;
-                rem |= row | (1ull << t);
-                alive = ~rem & inblk & (t == 63 ? 0ull : (~0ull << (t + 1)));
-            }
-            if ((kept >> lane) & 1ull) {
-                const int at = cnt + __popcll(kept & ((1ull << lane) - 1ull));
-                const int32_t id = kidx[i0 + lane];
-                seeds[at] = id;
-                sseed[at] = id;
-            }
-            cnt += __popcll(kept);
-            if (lane < KW)
-                for (unsigned long long k = kept; k;) {                  // four independent LDS reads per round (a repeated row is harmless)
-                    const int t0 = __builtin_ctzll(k);
-                    k &= k - 1ull;
-                    const int t1 = k ? __builtin_ctzll(k) : t0;
-                    k &= k - 1ull;
-                    const int t2 = k ? __builtin_ctzll(k) : t0;
-                    k &= k - 1ull;
-                    const int t3 = k ? __builtin_ctzll(k) : t0;
-                    k &= k - 1ull;
-                    removed |= (sup[(size_t)(i0 + t0) * KW + lane] | sup[(size_t)(i0 + t1) * KW + lane]) |
-                               (sup[(size_t)(i0 + t2) * KW + lane] | sup[(size_t)(i0 + t3) * KW + lane]);
-                }
-        }
-        for (int r = cnt + lane; r < K; r += 64) seeds[r] = -1;
-        if (lane == 0) {
-            L.n_seeds[c] = cnt;
-            s_misc[3] = cnt;
-        }
-    }
+    if (wave == 0) greedy_seed_scan(K, v, seeds, L.n_seeds + c, s_misc);
     __syncthreads();
     MCLK(0, wg_act, 3);
     if (!L.using_cim) return;                                            // MIST_label: the seeds are the pseudo ground truths
-
-    // ---- containment arg-max (heads.py:386-395): res[s] = the best-det proposal among {i : asy[i, seed_s] > con_thr and not huge(i)}
     const int n_seeds = s_misc[3];
-    const float thr = L.con_thr;
     int32_t* __restrict__ res = L.res + (size_t)c * K;
-    if (a.asy_t != nullptr) {
-        // Two seeds per wave and round, a lane takes 8 consecutive proposals per 512-proposal chunk: one 16-byte load per seed and
-        // chunk from the seed's row of the transposed map (rows padded to 8 entries: 16-byte aligned), all of a round's loads in
-        // flight before the first compare.
-        const int ldt = (N + 7) & ~7;
-        for (int s0 = wave * 2; s0 < K; s0 += 32) {
-            const bool on0 = s0 < n_seeds, on1 = s0 + 1 < n_seeds;       // (uniform per wave)
-            if (!on0) {
-                if (lane == 0) res[s0] = -1;
-                if (lane == 1 && s0 + 1 < K) res[s0 + 1] = -1;
-                continue;
-            }
-            const uint4* __restrict__ row0 = reinterpret_cast<const uint4*>(a.asy_t + (size_t)sseed[s0] * ldt);
-            const uint4* __restrict__ row1 = reinterpret_cast<const uint4*>(a.asy_t + (size_t)sseed[on1 ? s0 + 1 : s0] * ldt);
-            float best0 = -INFINITY, best1 = -INFINITY;
-            int bi0 = INT_MAX, bi1 = INT_MAX, any0 = 0, any1 = 0;
-            for (int i0 = lane * 8; i0 < ldt; i0 += 512) {
-                const uint4 v0 = row0[i0 >> 3], v1 = row1[i0 >> 3];
-                float d[8];
-                unsigned fl = 0;
-                if (lay.det_lds) {
-                    const float4 da = *reinterpret_cast<const float4*>(sdet + i0), db = *reinterpret_cast<const float4*>(sdet + i0 + 4);
-                    const uint2 fb = *reinterpret_cast<const uint2*>(sflag + i0);
-                    d[0] = da.x; d[1] = da.y; d[2] = da.z; d[3] = da.w; d[4] = db.x; d[5] = db.y; d[6] = db.z; d[7] = db.w;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) fl |= ((((e < 4 ? fb.x : fb.y) >> (8 * (e & 3))) & 0xffu) ? 1u : 0u) << e;
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const int i = i0 + e;
-                        d[e] = i < N ? L.det[(size_t)i * L.det_ld + L.det_off + c * L.det_cs] : 0.0f;
-                        fl |= (i < N && flag[i] ? 1u : 0u) << e;
-                    }
-                }
-                const unsigned w0[4] = {v0.x, v0.y, v0.z, v0.w}, w1[4] = {v1.x, v1.y, v1.z, v1.w};
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const int i = i0 + e;
-                    const bool in = i < N && ((fl >> e) & 1u);
-                    const bool c0 = in && h2f((uint16_t)(w0[e >> 1] >> (16 * (e & 1)))) > thr;
-                    const bool c1 = in && h2f((uint16_t)(w1[e >> 1] >> (16 * (e & 1)))) > thr;
-                    any0 |= c0;
-                    any1 |= c1;
-                    const float x0 = c0 ? d[e] : 0.0f, x1 = c1 ? d[e] : 0.0f;        // heads.py:393
-                    if (i < N && x0 > best0) { best0 = x0; bi0 = i; }                 // ascending i per lane: strict '>' keeps the first maximum
-                    if (i < N && x1 > best1) { best1 = x1; bi1 = i; }
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov0 = __shfl_xor(best0, o), ov1 = __shfl_xor(best1, o);
-                const int oi0 = __shfl_xor(bi0, o), oi1 = __shfl_xor(bi1, o);
-                if (ov0 > best0 || (ov0 == best0 && oi0 < bi0)) { best0 = ov0; bi0 = oi0; }
-                if (ov1 > best1 || (ov1 == best1 && oi1 < bi1)) { best1 = ov1; bi1 = oi1; }
-            }
-            any0 = __any(any0);
-            any1 = __any(any1);
-            if (lane == 0) res[s0] = any0 ? bi0 : -1;
-            if (lane == 1 && s0 + 1 < K) res[s0 + 1] = (on1 && any1) ? bi1 : -1;
-        }
-    } else {
-        for (int s = wave; s < K; s += 16) {                             // no transposed copy: strided reads of the map's column
-            if (s >= n_seeds) {
-                if (lane == 0) res[s] = -1;
-                continue;
-            }
-            const int seed = sseed[s];
-            float best = -INFINITY;
-            int besti = INT_MAX;
-            int any = 0;
-#pragma unroll 4
-            for (int i = lane; i < N; i += 64) {
-                const bool cond = (h2f(a.asy[(size_t)i * N + seed]) > thr) && flag[i];
-                any |= cond;
-                const float v = cond ? L.det[(size_t)i * L.det_ld + L.det_off + c * L.det_cs] : 0.0f;
-                if (v > best) {
-                    best = v;
-                    besti = i;
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(best, o);
-                const int oi = __shfl_xor(besti, o);
-                if (ov > best || (ov == best && oi < besti)) {
-                    best = ov;
-                    besti = oi;
-                }
-            }
-            any = __any(any);
-            if (lane == 0) res[s] = any ? besti : -1;
-        }
-    }
+    if (a.asy_t != nullptr) containment_argmax_transposed(a, L, lay.det_lds, v, flag, c, n_seeds, res);
+    else containment_argmax_strided(a, L, v, flag, c, n_seeds, res);
     MCLK(0, wg_act, 4);
 }
 
@@ -558,6 +577,9 @@ __device__ __forceinline__ void seed_phase(const cim_mining_args& a, const SeedL
 // The host draws the uniforms (np.random.random_sample) BEFORE the launch, at most `max_uniforms` of them, and
 // rewinds its generator to `used` afterwards (cim_amd/modeling/heads.py: RngLedger): same values, same stream position.
 
+// On purpose for the REST OF THE FILE (the arbitration's sums restate NumPy's: no fused multiply-adds; nothing below them - the
+// assignment, the host code - has a float multiply-add to fuse, and one added later stays unfused like its neighbours):
+#pragma clang fp contract(off)
 // numpy/core/src/umath/loops_utils.h.src, @TYPE@_pairwise_sum (PW_BLOCKSIZE = 128, 8 accumulators).  NumPy's version
 // recurses on halves above 128 elements; here the recursion is unrolled by a template depth (D = 4: n <= 2048).
 __device__ __forceinline__ float np_pairwise_leaf(const float* a, int n) {      // n <= 128
@@ -591,46 +613,71 @@ __device__ float np_pairwise_sum(const float* a, int n) {
     }
 }
 
-// Arbitration + sampling of layer l by ONE workgroup - the layer's LAST ARRIVING seed workgroup (round 4: a launch of its
-// own, one workgroup per layer).  Arbitration and the ordered compaction of a layer depend on nothing but that layer's
-// scores, so the layers run side by side; only the anti-noise sampling is ordered across layers, through the position in the
-// pre-drawn uniform stream: layer l consumes uniforms [base_l, base_l + G_l) with base_l = the sum of the earlier sampling
-// layers' list lengths (np.random.choice draws one double per class member, every member of the list belongs to exactly one
-// class).  Each arbitrator publishes its G_l in sync->gword[l] and reads the earlier layers' words: at most R <= 4 workgroups
-// ever wait, on workgroups that are running or will be dispatched whatever the waiters hold, and layer 0 waits for nobody.
-__device__ void arbitrate_phase(const cim_mining_args& a, MiningSync* __restrict__ sync, unsigned char* smem, int l, int n_act,
-                                const int16_t* __restrict__ s_act) {
-#pragma clang fp contract(off)                      // the sums below restate NumPy's: no fused multiply-adds
-    const int N = a.N, K = a.K, C = a.C, tid = threadIdx.x;
-    // LDS: cdf f64 [K] | part i32 [1024] | prob f32 [K] | pos i32 [K] | gclass i32 [N] | gweight f32 [N] | mark u8 [N]
-    double* cdf = reinterpret_cast<double*>(smem);
-    int32_t* part = reinterpret_cast<int32_t*>(cdf + K);
-    float* prob = reinterpret_cast<float*>(part + 1024);
-    int32_t* pos = reinterpret_cast<int32_t*>(prob + K);
-    int32_t* gclass = pos + K;
-    float* gweight = reinterpret_cast<float*>(gclass + N);
-    uint8_t* mark = reinterpret_cast<uint8_t*>(gweight + N);
-    __shared__ int s_used;
-    __shared__ float s_total;
-    __shared__ int s_err;
-    const int chunk = (N + 1023) / 1024;
-    const int lo = min(N, tid * chunk), hi = min(N, lo + chunk);
-    const cim_mining_layer& L = a.layer[l];
+// LDS of the arbitration phase (it re-uses the dynamic array from offset 0).  arb_layout is THE place its carve is computed, in
+// bytes and from the view's own element types: the host sizes the launch from `end`, arb_view adds the offsets to `smem`.
+struct ArbView {
+    double* cdf;                                     // f64 [K]
+    int32_t* part;                                   // i32 [1024] (the block scans' wave totals: 16 used)
+    float* prob;                                     // f32 [K]
+    int32_t* pos;                                    // i32 [K]
+    int32_t* gclass;                                 // i32 [N]
+    float* gweight;                                  // f32 [N], directly behind gclass
+    uint8_t* mark;                                   // u8 [N]
+    // the two arrays that lie over others: the arbitration's keys, decoded in place to gclass | gweight, and keep[j] of list position j
+    __host__ __device__ unsigned long long* key() const { return reinterpret_cast<unsigned long long*>(gclass); }
+    __host__ __device__ uint8_t* keep() const { return mark; }
+};
+struct ArbLayout {
+    size_t cdf, part, prob, pos, gclass, gweight, mark, end;
+};
+__host__ __device__ __forceinline__ ArbLayout arb_layout(int N, int K) {
+    ArbLayout o;
+    o.cdf = 0;
+    o.part = o.cdf + (size_t)K * sizeof(*ArbView{}.cdf);
+    o.prob = o.part + 1024 * sizeof(*ArbView{}.part);
+    o.pos = o.prob + (size_t)K * sizeof(*ArbView{}.prob);
+    o.gclass = o.pos + (size_t)K * sizeof(*ArbView{}.pos);
+    o.gweight = o.gclass + (size_t)N * sizeof(*ArbView{}.gclass);
+    o.mark = o.gweight + (size_t)N * sizeof(*ArbView{}.gweight);
+    o.end = o.mark + (size_t)N * sizeof(*ArbView{}.mark);
+    // key [N] fits in gclass [N] | gweight [N] (adjacent above), and starts 8-byte aligned: cdf is 8 K, the rest multiples of 4 in pairs
+    static_assert(sizeof(*ArbView{}.key()) <= sizeof(*ArbView{}.gclass) + sizeof(*ArbView{}.gweight), "key [] over gclass | gweight");
+    static_assert(sizeof(*ArbView{}.prob) == sizeof(*ArbView{}.pos) && sizeof(*ArbView{}.part) == 4, "key [] is 8-byte aligned");
+    return o;
+}
+__device__ __forceinline__ ArbView arb_view(unsigned char* smem, int N, int K) {
+    const ArbLayout o = arb_layout(N, K);
+    ArbView v;
+    v.cdf = reinterpret_cast<double*>(smem + o.cdf);
+    v.part = reinterpret_cast<int32_t*>(smem + o.part);
+    v.prob = reinterpret_cast<float*>(smem + o.prob);
+    v.pos = reinterpret_cast<int32_t*>(smem + o.pos);
+    v.gclass = reinterpret_cast<int32_t*>(smem + o.gclass);
+    v.gweight = reinterpret_cast<float*>(smem + o.gweight);
+    v.mark = smem + o.mark;
+    return v;
+}
 
-    MCLK(1, l, 0);
-    if (tid == 0) s_err = 0;
-    // (s_act[0 .. n_act): the image's classes, ascending - listed once at the start of the launch; the class loops below walk it)
-    (void)C;
-    // ---- arbitration (heads.py:397-405 / 306-314): the reference applies the image's classes one after the other in ascending
-    // order, `w > gt_weight` (strict) deciding - per proposal that is: the largest weight among the classes that list it, the
-    // LOWEST class on equal weights, and nothing unless w > -1 (heads.py:336).  All (class, candidate) pairs go through one
-    // LDS atomic max on key = (orderable(w) << 32) | ~(c + 1) (a proposal listed twice by a class - torch.unique's set
-    // semantics - just repeats its key); the initial key (orderable(-1), ~0) loses to any w > -1 and to nothing else.  NaN
-    // weights never win a strict '>': skipped.  The key array lies over gclass | gweight and is decoded in place through
-    // registers (N <= 8192: at most 8 keys per thread).
-    unsigned long long* key = reinterpret_cast<unsigned long long*>(gclass);
+// The arbitrator's words in static LDS
+struct ArbWords {
+    int used;                                        // position in the uniform stream
+    float total;                                     // a class's weight sum
+    int err;                                         // status bits of this layer
+};
+
+// Arbitration (heads.py:397-405 / 306-314): the reference applies the image's classes one after the other in ascending
+// order, `w > gt_weight` (strict) deciding - per proposal that is: the largest weight among the classes that list it, the
+// LOWEST class on equal weights, and nothing unless w > -1 (heads.py:336).  All (class, candidate) pairs go through one
+// LDS atomic max on key = (orderable(w) << 32) | ~(c + 1) (a proposal listed twice by a class - torch.unique's set
+// semantics - just repeats its key); the initial key (orderable(-1), ~0) loses to any w > -1 and to nothing else.  NaN
+// weights never win a strict '>': skipped.  The key array lies over gclass | gweight and is decoded in place through
+// registers (N <= 8192: at most 8 keys per thread).
+// (s_act[0 .. n_act): the image's classes, ascending - listed once at the start of the launch; the class loops walk it)
+__device__ __forceinline__ void arbitrate_classes(const cim_mining_layer& L, const ArbView& v, int N, int K, int l, int n_act,
+                                                  const int16_t* __restrict__ s_act) {
+    const int tid = threadIdx.x;
     const unsigned long long key0 = ((unsigned long long)orderable(-1.0f) << 32) | 0xffffffffull;
-    for (int i = tid; i < N; i += 1024) key[i] = key0;
+    for (int i = tid; i < N; i += 1024) v.key()[i] = key0;
     __syncthreads();
     MCLK(1, l, 1);
     const int32_t* __restrict__ cand = L.using_cim ? L.res : L.seeds;
@@ -640,191 +687,222 @@ __device__ void arbitrate_phase(const cim_mining_args& a, MiningSync* __restrict
         if (p < 0) continue;
         float w = L.wa[(size_t)p * L.wa_ld + L.wa_off + c];
         if (L.wb) w = w * L.wb[(size_t)p * L.wb_ld + L.wb_off + c * L.wb_cs];       // preds = cls * det, heads.py:330
-        if (w == w) atomicMax(key + p, ((unsigned long long)orderable(w) << 32) | (unsigned)~(c + 1));
+        if (w == w) atomicMax(v.key() + p, ((unsigned long long)orderable(w) << 32) | (unsigned)~(c + 1));
     }
     __syncthreads();
     MCLK(1, l, 2);
-    {
-        unsigned long long kreg[8];
+    unsigned long long kreg[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int i = tid + u * 1024;
-            kreg[u] = i < N ? key[i] : key0;
-        }
-        __syncthreads();
+    for (int u = 0; u < 8; ++u) {
+        const int i = tid + u * 1024;
+        kreg[u] = i < N ? v.key()[i] : key0;
+    }
+    __syncthreads();
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int i = tid + u * 1024;
-            if (i < N) {
-                const int gc = (int)~(unsigned)kreg[u];
-                const unsigned o = (unsigned)(kreg[u] >> 32);
-                const float gw = gc > 0 ? __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o) : -1.0f;   // orderable^-1
-                gclass[i] = gc;
-                gweight[i] = gw;
-                L.gt_class[i] = gc;
-                L.gt_weight[i] = gw;
-            }
+    for (int u = 0; u < 8; ++u) {
+        const int i = tid + u * 1024;
+        if (i < N) {
+            const int gc = (int)~(unsigned)kreg[u];
+            const float gw = gc > 0 ? orderable_inverse((unsigned)(kreg[u] >> 32)) : -1.0f;
+            v.gclass[i] = gc;
+            v.gweight[i] = gw;
+            L.gt_class[i] = gc;
+            L.gt_weight[i] = gw;
         }
     }
+}
+
+// This layer's share of the uniform stream (`share` doubles) is published, and where it starts is read: the sum of the
+// earlier layers' shares.  One lane.
+__device__ __forceinline__ int publish_and_wait_base(MiningSync* __restrict__ sync, int l, int share) {
+    __hip_atomic_store(sync->gword + l, (1ull << 63) | (unsigned long long)share, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    int base = 0;
+    for (int e = 0; e < l; ++e) {
+        unsigned long long v;
+        do {
+            v = __hip_atomic_load(sync->gword + e, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+            if (!(v >> 63)) __builtin_amdgcn_s_sleep(2);
+        } while (!(v >> 63));
+        base += (int)(v & 0xfffffull);
+    }
+    return base;
+}
+
+// Anti-noise sampling of ONE class (heads.py:451-466): thread t owns the proposals [lo, hi) and the list positions from p0 on
+__device__ __forceinline__ void sample_class(const cim_mining_args& a, const ArbView& v, ArbWords& s, int c, int lo, int hi, int p0) {
+    const int tid = threadIdx.x, K = a.K;
+    // members of class c in list order
+    int m = 0;
+    for (int i = lo; i < hi; ++i) m += v.gclass[i] == c + 1;
+    int Gc;
+    int q0 = block_exclusive_scan(m, v.part, &Gc);
+    if (Gc == 0) return;                                                 // heads.py:454-455 (uniform)
+    if (Gc > K) {                                                        // cannot happen (<= K candidates per class); stay memory-safe:
+        if (tid == 0) {                                                  // the step fails with status bit 1, the uniforms count as drawn
+            s.err |= 1;
+            s.used += Gc;
+        }
+        __syncthreads();
+        return;
+    }
+    // this class's uniforms: the load flies under the sums below
+    const int ubase = s.used;
+    const bool u_ok = ubase + Gc <= a.max_uniforms;
+    const double u_first = (u_ok && tid < Gc) ? a.uniforms[ubase + tid] : 0.0;
+    for (int i = lo, j = p0; i < hi; ++i) {
+        const int gc = v.gclass[i];
+        if (gc == c + 1) {
+            v.pos[q0] = j;
+            v.prob[q0] = v.gweight[i];
+            v.keep()[j] = 0;                                               // inds[class_idx] = 0
+            ++q0;
+        }
+        j += gc > 0;
+    }
+    __syncthreads();
+    if (tid == 0) s.total = np_pairwise_sum<4>(v.prob, Gc);
+    __syncthreads();
+    const float total = s.total;
+    // p = prob / total in f32 (== the f64 quotient rounded once), then np.cumsum in f64: a strictly sequential sum
+    // (out[0] = p[0]).  The divisions are done by everybody; the chain that is left for one lane is load / add / store,
+    // eight loads ahead of the additions.
+    double* cdf = v.cdf;
+    for (int j = tid; j < Gc; j += 1024) cdf[j] = (double)(float)((double)v.prob[j] / (double)total);
+    __syncthreads();
+    if (tid == 0) {
+        double acc = cdf[0];
+        int j = 1;
+        for (; j + 8 <= Gc; j += 8) {
+            double x[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) x[u] = cdf[j + u];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                acc += x[u];
+                cdf[j + u] = acc;
+            }
+        }
+        for (; j < Gc; ++j) {
+            acc += cdf[j];
+            cdf[j] = acc;
+        }
+    }
+    __syncthreads();
+    const double last = cdf[Gc - 1];
+    if (!u_ok) {                                                         // the host drew too few (cannot happen: bound = R * min(N, classes * K))
+        if (tid == 0) s.err |= 2;
+    } else {
+        for (int j = tid; j < Gc; j += 1024) {
+            const double u = j == tid ? u_first : a.uniforms[ubase + j];
+            int b = 0, e = Gc;                                           // searchsorted(cdf / cdf[-1], u, side='right'): first index with cdf > u
+            while (b < e) {
+                const int mid = (b + e) >> 1;
+                if (cdf[mid] / last <= u) b = mid + 1; else e = mid;
+            }
+            if (b >= Gc) b = Gc - 1;                                     // u < 1 == cdf[-1]: unreachable; memory safety
+            v.keep()[v.pos[b]] = 1;                                        // inds[np.unique(sampled)] = 1
+        }
+    }
+    __syncthreads();
+    if (tid == 0) s.used = ubase + Gc;
+}
+
+// Survivors, in list order -> post-sampling list; returns their number
+__device__ __forceinline__ int write_survivors(const cim_mining_layer& L, const ArbView& v, int lo, int hi, int p0, int cnt) {
+    int m = 0;
+    for (int j = p0; j < p0 + cnt; ++j) m += v.keep()[j];
+    int Gk;
+    int q0 = block_exclusive_scan(m, v.part, &Gk);
+    for (int i = lo, j = p0; i < hi; ++i) {
+        const int gc = v.gclass[i];
+        if (gc > 0) {
+            const uint8_t kp = v.keep()[j];
+            L.pre_keep[j] = kp;
+            if (kp) {
+                L.gt_idx[q0] = i;
+                L.gt_cls[q0] = gc;
+                L.gt_w[q0] = v.gweight[i];
+                ++q0;
+            }
+            ++j;
+        }
+    }
+    return Gk;
+}
+
+// The layer's counts; one lane.  This arbitrator is done.  Its error bits travel in its word; the LAST of the R arbitrators to
+// finish writes the step's status word (the losses launch ORs its own bits into it later) and puts every sync word back to
+// zero - all R have read what they needed by then, and every seed workgroup has arrived (each layer's arbitrator was
+// elected by its last arrival): the scratch is as the caller handed it over.
+__device__ __forceinline__ void finish_layer(const cim_mining_args& a, MiningSync* __restrict__ sync, int l, int G, int Gk,
+                                             const ArbWords& s) {
+    const cim_mining_layer& L = a.layer[l];
+    L.counts[0] = G;
+    L.counts[1] = Gk;
+    a.layer_valid[l] = G > 0 ? 1 : 0;                                    // heads.py:429-430: no pseudo GT -> layer skipped
+    if (l == a.R - 1) a.used[0] = s.used;                                // (the last layer ends where the whole step's stream ends)
+    if (s.err) __hip_atomic_fetch_or(sync->gword + l, (unsigned long long)s.err << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned fin = __hip_atomic_fetch_add(&sync->done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (fin == (unsigned)a.R - 1u) {
+        int bits = 0;
+        for (int e = 0; e < a.R; ++e) {
+            bits |= (int)((__hip_atomic_load(sync->gword + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 32) & 0xffu);
+            __hip_atomic_store(sync->gword + e, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(sync->arrive + e, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __hip_atomic_store(&sync->done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *a.status = bits;
+    }
+}
+
+// Arbitration + sampling of layer l by ONE workgroup - the layer's LAST ARRIVING seed workgroup (round 4: a launch of its
+// own, one workgroup per layer).  Arbitration and the ordered compaction of a layer depend on nothing but that layer's
+// scores, so the layers run side by side; only the anti-noise sampling is ordered across layers, through the position in the
+// pre-drawn uniform stream: layer l consumes uniforms [base_l, base_l + G_l) with base_l = the sum of the earlier sampling
+// layers' list lengths (np.random.choice draws one double per class member, every member of the list belongs to exactly one
+// class).  Each arbitrator publishes its G_l in sync->gword[l] and reads the earlier layers' words: at most R <= 4 workgroups
+// ever wait, on workgroups that are running or will be dispatched whatever the waiters hold, and layer 0 waits for nobody.
+__device__ void arbitrate_phase(const cim_mining_args& a, MiningSync* __restrict__ sync, unsigned char* smem, int l, int n_act,
+                                const int16_t* __restrict__ s_act) {
+    const int N = a.N, K = a.K, tid = threadIdx.x;
+    const ArbView v = arb_view(smem, N, K);
+    __shared__ ArbWords s;
+    const int chunk = (N + 1023) / 1024;
+    const int lo = min(N, tid * chunk), hi = min(N, lo + chunk);
+    const cim_mining_layer& L = a.layer[l];
+
+    MCLK(1, l, 0);
+    if (tid == 0) s.err = 0;
+    arbitrate_classes(L, v, N, K, l, n_act, s_act);
     __syncthreads();
     MCLK(1, l, 3);
     // ---- ordered compaction of {i : gclass[i] > 0} -> pre-sampling list (ascending proposal index).  Thread t owns the
     // proposals [lo, hi) and therefore the list positions [p0, p0 + cnt): every later pass walks the list through gclass /
     // gweight in LDS and these two numbers, never through the list in global memory.
     int cnt = 0;
-    for (int i = lo; i < hi; ++i) cnt += gclass[i] > 0;
-    int G;
-    const int p0 = block_exclusive_scan(cnt, part, &G);
+    for (int i = lo; i < hi; ++i) cnt += v.gclass[i] > 0;
+    int Gv;
+    const int p0 = block_exclusive_scan(cnt, v.part, &Gv);
+    const int G = __builtin_amdgcn_readfirstlane(Gv);                    // (uniform; a scalar across the sampling loop: no spill)
     // ---- this layer's share of the uniform stream, and where it starts
     const bool sampling = L.anti_noise && G > 0;
     MCLK(1, l, 4);
-    if (tid == 0) {
-        __hip_atomic_store(sync->gword + l, (1ull << 63) | (unsigned long long)(sampling ? G : 0), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        int base = 0;
-        for (int e = 0; e < l; ++e) {
-            unsigned long long v;
-            do {
-                v = __hip_atomic_load(sync->gword + e, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-                if (!(v >> 63)) __builtin_amdgcn_s_sleep(2);
-            } while (!(v >> 63));
-            base += (int)(v & 0xfffffull);
-        }
-        s_used = base;
-    }
+    if (tid == 0) s.used = publish_and_wait_base(sync, l, sampling ? G : 0);
     MCLK(1, l, 5);
-    uint8_t* __restrict__ keep = mark;                                   // keep[j], j = list position (mark[] is dead after the arbitration)
     for (int i = lo, j = p0; i < hi; ++i)
-        if (gclass[i] > 0) {
+        if (v.gclass[i] > 0) {
             L.pre_idx[j] = i;
-            keep[j] = 1;
+            v.keep()[j] = 1;
             ++j;
         }
-    __syncthreads();                                                     // keep[], s_used
+    __syncthreads();                                                     // keep[], s.used
     MCLK(1, l, 6);
     // ---- anti-noise sampling, class by class in ascending order (heads.py:451-466)
-    if (sampling) {
-        for (int ac = 0; ac < n_act; ++ac) {
-            const int c = s_act[ac];
-            // members of class c in list order
-            int m = 0;
-            for (int i = lo; i < hi; ++i) m += gclass[i] == c + 1;
-            int Gc;
-            int q0 = block_exclusive_scan(m, part, &Gc);
-            if (Gc == 0) continue;                                       // heads.py:454-455 (uniform)
-            if (Gc > K) {                                                // cannot happen (<= K candidates per class); stay memory-safe:
-                if (tid == 0) {                                          // the step fails with status bit 1, the uniforms count as drawn
-                    s_err |= 1;
-                    s_used += Gc;
-                }
-                __syncthreads();
-                continue;
-            }
-            // this class's uniforms: the load flies under the sums below
-            const int ubase = s_used;
-            const bool u_ok = ubase + Gc <= a.max_uniforms;
-            const double u_first = (u_ok && tid < Gc) ? a.uniforms[ubase + tid] : 0.0;
-            for (int i = lo, j = p0; i < hi; ++i) {
-                const int gc = gclass[i];
-                if (gc == c + 1) {
-                    pos[q0] = j;
-                    prob[q0] = gweight[i];
-                    keep[j] = 0;                                         // inds[class_idx] = 0
-                    ++q0;
-                }
-                j += gc > 0;
-            }
-            __syncthreads();
-            if (tid == 0) s_total = np_pairwise_sum<4>(prob, Gc);
-            __syncthreads();
-            const float total = s_total;
-            // p = prob / total in f32 (== the f64 quotient rounded once), then np.cumsum in f64: a strictly sequential sum
-            // (out[0] = p[0]).  The divisions are done by everybody; the chain that is left for one lane is load / add / store,
-            // eight loads ahead of the additions.
-            for (int j = tid; j < Gc; j += 1024) cdf[j] = (double)(float)((double)prob[j] / (double)total);
-            __syncthreads();
-            if (tid == 0) {
-                double acc = cdf[0];
-                int j = 1;
-                for (; j + 8 <= Gc; j += 8) {
-                    double x[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) x[u] = cdf[j + u];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        acc += x[u];
-                        cdf[j + u] = acc;
-                    }
-                }
-                for (; j < Gc; ++j) {
-                    acc += cdf[j];
-                    cdf[j] = acc;
-                }
-            }
-            __syncthreads();
-            const double last = cdf[Gc - 1];
-            const int base = ubase;
-            if (!u_ok) {                                                 // the host drew too few (cannot happen: bound = R * min(N, classes * K))
-                if (tid == 0) s_err |= 2;
-            } else {
-                for (int j = tid; j < Gc; j += 1024) {
-                    const double u = j == tid ? u_first : a.uniforms[base + j];
-                    int b = 0, e = Gc;                                   // searchsorted(cdf / cdf[-1], u, side='right'): first index with cdf > u
-                    while (b < e) {
-                        const int mid = (b + e) >> 1;
-                        if (cdf[mid] / last <= u) b = mid + 1; else e = mid;
-                    }
-                    if (b >= Gc) b = Gc - 1;                             // u < 1 == cdf[-1]: unreachable; memory safety
-                    keep[pos[b]] = 1;                                    // inds[np.unique(sampled)] = 1
-                }
-            }
-            __syncthreads();
-            if (tid == 0) s_used = base + Gc;
-        }
-    }
+    if (sampling)
+        for (int ac = 0; ac < n_act; ++ac) sample_class(a, v, s, s_act[ac], lo, hi, p0);
     MCLK(1, l, 7);
-    // ---- survivors, in list order -> post-sampling list
-    {
-        int m = 0;
-        for (int j = p0; j < p0 + cnt; ++j) m += keep[j];
-        int Gk;
-        int q0 = block_exclusive_scan(m, part, &Gk);
-        for (int i = lo, j = p0; i < hi; ++i) {
-            const int gc = gclass[i];
-            if (gc > 0) {
-                const uint8_t kp = keep[j];
-                L.pre_keep[j] = kp;
-                if (kp) {
-                    L.gt_idx[q0] = i;
-                    L.gt_cls[q0] = gc;
-                    L.gt_w[q0] = gweight[i];
-                    ++q0;
-                }
-                ++j;
-            }
-        }
-        if (tid == 0) {
-            L.counts[0] = G;
-            L.counts[1] = Gk;
-            a.layer_valid[l] = G > 0 ? 1 : 0;                            // heads.py:429-430: no pseudo GT -> layer skipped
-            if (l == a.R - 1) a.used[0] = s_used;                        // (the last layer ends where the whole step's stream ends)
-            // This arbitrator is done.  Its error bits travel in its word; the LAST of the R arbitrators to finish writes the
-            // step's status word (the losses launch ORs its own bits into it later) and puts every sync word back to zero -
-            // all R have read what they needed by then, and every seed workgroup has arrived (each layer's arbitrator was
-            // elected by its last arrival): the scratch is as the caller handed it over.
-            if (s_err) __hip_atomic_fetch_or(sync->gword + l, (unsigned long long)s_err << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned fin = __hip_atomic_fetch_add(&sync->done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            if (fin == (unsigned)a.R - 1u) {
-                int bits = 0;
-                for (int e = 0; e < a.R; ++e) {
-                    bits |= (int)((__hip_atomic_load(sync->gword + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 32) & 0xffu);
-                    __hip_atomic_store(sync->gword + e, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(sync->arrive + e, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                __hip_atomic_store(&sync->done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                *a.status = bits;
-            }
-        }
-    }
+    const int Gk = write_survivors(L, v, lo, hi, p0, cnt);
+    if (tid == 0) finish_layer(a, sync, l, G, Gk, s);
     MCLK(1, l, 8);
 }
 
@@ -873,7 +951,7 @@ __device__ __forceinline__ void assign_row(const uint16_t* __restrict__ r, int r
                                            int32_t* __restrict__ max_idx) {
     float best = -INFINITY;
     int bestj = INT_MAX;
-    uint16_t bestbits = 0;
+    int bestbits = 0;                                                    // (the winner's binary16 bits travel with it)
     for (int j = lane; j < G; j += 64) {
         const uint16_t bits = r[gt_idx[j]];
         const float v = h2f(bits);
@@ -883,21 +961,11 @@ __device__ __forceinline__ void assign_row(const uint16_t* __restrict__ r, int r
             bestbits = bits;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o);
-        const int oj = __shfl_xor(bestj, o);
-        const int ob = __shfl_xor((int)bestbits, o);
-        if (ov > best || (ov == best && oj < bestj)) {
-            best = ov;
-            bestj = oj;
-            bestbits = (uint16_t)ob;
-        }
-    }
+    wave_argmax(best, bestj, bestbits);
     if (bestj == INT_MAX) {  // every gathered value was NaN: keep memory-safe, pick column 0
         bestj = 0;
         bestbits = r[gt_idx[0]];
-        best = h2f(bestbits);
+        best = h2f((uint16_t)bestbits);
     }
     const bool ignore = (best == 0.0f);                                 // heads.py:484
     const bool bg = (best < cls_thr) && !ignore;                        // heads.py:489
@@ -907,7 +975,7 @@ __device__ __forceinline__ void assign_row(const uint16_t* __restrict__ r, int r
         loss_w[row] = ignore ? 0.0f : gt_w[bestj];                      // heads.py:480,486
         max_idx[row] = bestj;
         // heads.py:500-501, literally: (> thr) -> 1, then (<= thr) -> 0
-        uint16_t bits = bestbits;
+        uint16_t bits = (uint16_t)bestbits;
         float v = best;
         if (v > iou_thr) { bits = 0x3C00; v = 1.0f; }
         if (v <= iou_thr) bits = 0;
@@ -927,7 +995,7 @@ __global__ __launch_bounds__(256) void step_assign_kernel(const cim_mining_args 
 }
 
 long long arbitrate_lds_bytes(int N, int K) {
-    return (long long)K * 8 + 1024 * 4 + (long long)K * 8 + (long long)N * 9 + 16;
+    return (long long)arb_layout(N, K).end + 16;                         // (16 bytes of slack, as ever)
 }
 
 SeedLayout seed_layout(int N, int K) {

@@ -101,6 +101,31 @@ def test_layout_boundaries():
                 assert lay(n, k) == mc.seed_layout(n, k), (n, k)
 
 
+# cim_mining_lds_bytes(N, K): the dynamic LDS of the mining launch = max(seed carve, arbitration carve), pinned as literals
+LDS_BYTES = {
+    # every (N, K) of CASES
+    (64, 7): 6912, (70, 7): 7216, (200, 20): 12240, (300, 30): 16320, (301, 31): 16368, (500, 50): 24208, (1001, 101): 44640,
+    (1500, 150): 66000, (2041, 205): 89728, (2043, 205): 25779, (2049, 205): 25833, (2561, 257): 31360,
+    (2040, 204): 89632,                              # 255 / 256 (above) sixteen-byte pieces per streamed row: the last two row_lds sizes
+    (2000, 256): 90640, (2000, 257): 28528,          # KW = 4 / 5
+    (2456, 1024): 163840, (2457, 1024): 151552,      # the largest N with the detector column in LDS at K = 1024, and the next
+    (8192, 820): 143456, (8192, 1024): 151552,
+    (8192, 64): 78864, (4096, 16): 41232,            # the arbitration carve (16 K + 4096 + 9 N + 16) above the seed carve
+    (1, 1): 4448,
+}
+
+
+def test_lds_bytes_are_pinned():
+    from cim_amd import _lib
+    assert {(c["n"], int(np.ceil(0.1 * c["n"]))) for c in CASES.values()} <= set(LDS_BYTES)
+    for (n, k), want in LDS_BYTES.items():
+        assert int(_lib.call("cim_mining_lds_bytes", n, k)) == want, (n, k)
+    arb = lambda n, k: 16 * k + 4096 + 9 * n + 16
+    assert LDS_BYTES[8192, 64] == arb(8192, 64) and LDS_BYTES[4096, 16] == arb(4096, 16) and LDS_BYTES[8192, 820] > arb(8192, 820)
+    lay = lambda n, k: int(_lib.call("cim_mining_layout", n, k))
+    assert [lay(2456, 1024) & 1, lay(2457, 1024) & 1] == [1, 0]
+
+
 # ------------------------------------------------------------------ ties at the top-K boundary
 def _boundary(case, q):
     col, k = _col(case, q), case["K"]
