@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from ..core.config import cfg
-from ..ops import conv1x1_bn_act, conv3x3_bn_act, conv7x7_bn_act, max_pool2d
+from ..ops import conv1x1_bn_act, conv3x3_bn_act, conv7x7_bn_act, conv7x7_bn_act_train, max_pool2d
 from ..ops.conv3x3 import prefetch_transposed_weights
 from .maskfuse import MaskFuse  # noqa: F401  (resolved as "resnet50.MaskFuse" by get_func)
 
@@ -127,12 +127,14 @@ class resnet(nn.Module):
     def forward(self, x):
         if self.training and torch.is_grad_enabled():
             # the transposed 3 x 3 weights the backward's data gradients read: one launch beside the forward (ops/conv3x3.py)
-            prefetch_transposed_weights([b.conv2 for i in range(cfg.ResNet.FREEZE_AT + 1, self.block_counts + 1)
+            prefetch_transposed_weights([b.conv2 for i in range(max(cfg.ResNet.FREEZE_AT, 1) + 1, self.block_counts + 1)      # (res1 has no 3 x 3)
                                          for b in getattr(self, "res%d" % i)])
         for i in range(self.block_counts):
             m = getattr(self, "res%d" % (i + 1))
             if i == 0:      # the stem: 7 x 7 convolution + BatchNorm + ReLU in one launch (frozen: forward only), then the max-pool (csrc/pool.hip)
-                x = max_pool2d(conv7x7_bn_act(x, m[0], m[1], relu=True), m[3])
+                # FREEZE_AT = 0: the stem trains - convolution, BatchNorm launch and the 7 x 7 weight gradient (ops/conv3x3.py)
+                trains = x.is_cuda and torch.is_grad_enabled() and (m[0].weight.requires_grad or m[1].weight.requires_grad or m[1].bias.requires_grad)
+                x = max_pool2d((conv7x7_bn_act_train if trains else conv7x7_bn_act)(x, m[0], m[1], relu=True), m[3])
             else:
                 x = m(x)
         return x

@@ -16,6 +16,7 @@ from torch.autograd import Function
 
 from .. import _lib
 from . import chain
+from .bn_act import BnActFunction
 from . import fallback
 from .conv1x1 import affine_outputs
 from . import gemm as _gemm_mod
@@ -229,3 +230,71 @@ def conv7x7_bn_act(x, conv, bn, relu=True):
                       bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.eps),
                       int(relu), _lib.stream_ptr())
     return y
+
+
+# ---- the stem that trains (FREEZE_AT = 0; the PRM network after prm_train.unfreeze) ----------------------------------------------
+
+class Conv7x7Function(Function):
+    """The bare 7 x 7 convolution with a weight gradient: forward = the stem kernel with the identity BatchNorm (a = 1, b = 0
+    exactly), backward = csrc/conv7x7_dw.hip.  No data gradient: the stem's input is the image."""
+
+    @staticmethod
+    def forward(ctx, x, w, stride):
+        B, cin, H, W = x.shape
+        cout = w.shape[0]
+        key = (x.device, cout)
+        if key not in _IDENTITY_BN:
+            _IDENTITY_BN[key] = (torch.ones(cout, device=x.device), torch.zeros(cout, device=x.device))
+        ones, zeros = _IDENTITY_BN[key]
+        y = torch.empty((B, cout, (H - 1) // stride + 1, (W - 1) // stride + 1), dtype=torch.float32, device=x.device)
+        st = _lib.stream_ptr()
+        for b in range(B):
+            _lib.call("cim_conv7x7_nchw_f32", x[b].data_ptr(), w.data_ptr(), y[b].data_ptr(), cin, cout, H, W, stride,
+                      ones.data_ptr(), zeros.data_ptr(), zeros.data_ptr(), ones.data_ptr(), 0.0, 0, st)
+        ctx.save_for_backward(x)
+        ctx.cfg = (B, cin, cout, H, W, stride)
+        return y
+
+    @staticmethod
+    def backward(ctx, dconv):
+        x, = ctx.saved_tensors
+        cfg = ctx.cfg
+        B, cin, cout = cfg[:3]
+        dconv = dconv.contiguous()
+        ws = torch.empty(_lib.call("cim_conv7x7_dw_workspace", *cfg) // 4, dtype=torch.float32, device=x.device)
+        dw = torch.empty((cout, cin, 7, 7), dtype=torch.float32, device=x.device)
+        _lib.call("cim_conv7x7_dw_f32", dconv.data_ptr(), x.data_ptr(), dw.data_ptr(), *cfg, ws.data_ptr(), _lib.stream_ptr())
+        return None, dw, None
+
+
+def conv7x7_bn_act_train(x, conv, bn, relu=True):
+    """relu?(bn(conv(x))) for a 7 x 7 stem convolution (padding 3, stride 1 / 2, no bias, 1..4 input channels) whose weight and
+    BatchNorm affine may TRAIN; the BatchNorm's statistics stay frozen (eval mode).  Forward: the stem kernel without its
+    epilogue, then the `bn_act` launch; backward: `bn_act`'s (dconv, dgamma, dbeta), then the weight gradient on the matrix pipe -
+    returned through autograd, so hooks on the weight see it.  With nothing to train it is `conv7x7_bn_act`.  There is no data
+    gradient and no second path: an input that requires a gradient, a BatchNorm in training mode, a bias, an unsupported
+    geometry or CPU tensors raise ValueError."""
+    who = "cim_amd.ops.conv7x7_bn_act_train: "
+    if not (torch.is_tensor(x) and x.is_cuda and conv.weight.is_cuda and bn.weight is not None and bn.weight.is_cuda):
+        raise ValueError(who + "CUDA/HIP tensors expected (no CPU path)")
+    if bn.training or not (bn.affine and bn.track_running_stats):
+        raise ValueError(who + "the BatchNorm must be in eval() mode with running statistics (training-mode BatchNorm is not built)")
+    if conv.bias is not None:
+        raise ValueError(who + "a convolution bias is not supported")
+    grad_on = torch.is_grad_enabled()
+    if grad_on and x.requires_grad:
+        raise ValueError(who + "the input requires a gradient: the stem's data gradient is not built")
+    if not (x.dtype == torch.float32 and x.dim() == 4 and conv.kernel_size == (7, 7) and conv.padding == (3, 3)
+            and conv.stride in ((1, 1), (2, 2)) and conv.dilation == (1, 1) and conv.groups == 1 and 1 <= conv.in_channels <= 4
+            and 1 <= conv.out_channels <= 256 and x.shape[3] <= 4096 and x.shape[2] * x.shape[3] < (1 << 20)):
+        raise ValueError(who + "unsupported geometry %s on an input of shape %s" % (conv, tuple(x.shape)))
+    if not (grad_on and (conv.weight.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad)):
+        return conv7x7_bn_act(x, conv, bn, relu=relu)
+    x = x.contiguous()
+    w = conv.weight if conv.weight.is_contiguous() else conv.weight.contiguous()
+    if w.requires_grad:
+        z = Conv7x7Function.apply(x, w, conv.stride[0])
+    else:
+        with torch.no_grad():
+            z = Conv7x7Function.apply(x, w, conv.stride[0])
+    return BnActFunction.apply(z, None, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, relu)

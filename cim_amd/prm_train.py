@@ -8,19 +8,21 @@ detector's body trains on.
 
     model = prm.PeakResponseMapping(prm.fc_resnet50(num_classes=20))     # the same object `cim_amd.prm.peaks` takes
     prm_train.freeze(model)                                              # stem and layer1, as the detector's body
+    # prm_train.unfreeze(model)                                          # or: every layer trains, the reference's state
     loss = prm_train.loss(model, images, target)                         # images [B,3,S,S'] (prm.network_input*), target [B,C]
     loss.backward()
 
 `cim_amd.prm.PeakResponseMapping` itself stays the inference object (its train() raises, its forward runs under no_grad): a
-checkpoint moves between the two entries unchanged.  BatchNorm statistics stay frozen (the reference's train() updates them),
-the stem never trains (its kernel is forward only).  Takes DEVICE tensors; a CPU tensor is an error (no CPU fallback)."""
+checkpoint moves between the two entries unchanged.  BatchNorm statistics stay frozen (the reference's train() updates them).
+A stem that trains takes `ops.conv7x7_bn_act_train` (the 7 x 7 weight gradient of csrc/conv7x7_dw.hip).
+Takes DEVICE tensors; a CPU tensor is an error (no CPU fallback)."""
 import numpy as np
 import torch
 from torch.autograd import Function
 
 from . import _lib
 from . import prm as _prm
-from .ops import conv1x1_bn_act, conv7x7_bn_act, max_pool2d
+from .ops import conv1x1_bn_act, conv7x7_bn_act, conv7x7_bn_act_train, max_pool2d
 
 STIM_MAX_HW = _lib.CONSTANTS["CIM_PRM_STIM_MAX_HW"]
 STATUS_NAN, STATUS_NO_PEAK = _prm.STATUS_NAN, _prm.STATUS_NO_PEAK
@@ -136,13 +138,23 @@ def multilabel_soft_margin_loss(aggregation, target):
 
 def freeze(model, at=2):
     """requires_grad = False on the stem and on layer1 .. layer{at-1} of the PeakResponseMapping `model` (at in 2..5; 2 = the
-    stage up to which the detector's body freezes, ResNet.FREEZE_AT).  The stem is always frozen: its kernel is forward only."""
+    stage up to which the detector's body freezes, ResNet.FREEZE_AT).  It only ever freezes: parameters behind `at` keep their
+    state.  `unfreeze` is the way back to a network whose stem and layer1 train."""
     if at not in (2, 3, 4, 5):
         raise ValueError("cim_amd.prm_train.freeze: at = %r, one of 2, 3, 4, 5 is needed" % (at,))
     f = _features(model)
     for i in range(0, 3 + at):               # features: conv1, bn1, relu, maxpool, layer1 (index 4) ..
         for p in f[i].parameters():
             p.requires_grad = False
+    return model
+
+
+def unfreeze(model):
+    """requires_grad = True on EVERY parameter of the PeakResponseMapping `model`: the reference's training state
+    (lib/prm/prm_model.py trains every layer).  BatchNorm statistics still stay frozen."""
+    _features(model)
+    for p in model.parameters():
+        p.requires_grad = True
     return model
 
 
@@ -166,13 +178,13 @@ def _identity_bn(device, c):
 
 
 def class_response_maps(model, images):
-    """model[0] under the current grad mode: the stem (forward only), layer1..layer4 and the 1 x 1 classifier on the fused launches,
-    the classifier WITH autograd - its convolution bias folded into the identity BatchNorm's mean (ops/conv1x1.py), its weight
-    and bias gradients from the small-tile GEMM path."""
+    """model[0] under the current grad mode: the stem (one fused launch when frozen, its training form when one of its parameters
+    requires a gradient), layer1..layer4 and the 1 x 1 classifier on the fused launches, the classifier WITH autograd - its
+    convolution bias folded into the identity BatchNorm's mean (ops/conv1x1.py), its weight and bias gradients from the small-tile
+    GEMM path."""
     f = _features(model)
-    if any(p.requires_grad for i in range(4) for p in f[i].parameters()) and torch.is_grad_enabled():
-        raise ValueError("cim_amd.prm_train: the stem cannot train (conv7x7_bn_act is forward only): call prm_train.freeze(model) first")
-    x = max_pool2d(conv7x7_bn_act(images, f[0], f[1], relu=True), f[3])
+    trains = torch.is_grad_enabled() and any(p.requires_grad for i in range(4) for p in f[i].parameters())
+    x = max_pool2d((conv7x7_bn_act_train if trains else conv7x7_bn_act)(images, f[0], f[1], relu=True), f[3])
     for i in range(4, 8):
         x = f[i](x)
     conv = model[0].classifier[0]

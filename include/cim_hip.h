@@ -745,6 +745,20 @@ int cim_conv3x3_nchw_bn_act_bwd(const float* dy, const float* y, const float* x_
 typedef struct { const float* w; float* wt; int cin; int cout; } cim_wt_desc;
 int cim_conv3x3_wt_multi(const cim_wt_desc* descs, int n, void* stream);
 
+/* Weight gradient of the 7 x 7 stem convolution (padding 3, stride 1 or 2, no bias; torchvision ResNet conv1 with FREEZE_AT = 0,
+ * lib/modeling/resnet50.py, and lib/prm/prm_model.py fc_resnet50, whose stem trains), B images in one call (csrc/conv7x7_dw.hip):
+ *   dw[co][ci][ky][kx] = sum over b, oy, ox of dconv[b][co][oy][ox] * x[b][ci][oy stride + ky - 3][ox stride + kx - 3]
+ * dconv [B][cout][Ho][Wo] is the gradient of the convolution's output (what cim_bn_act_bwd leaves as dx), Ho = (H-1)/stride + 1;
+ * x [B][cin][H][W]; dw [cout][cin][7][7] is WRITTEN, not accumulated.  True fp32 products on the matrix pipe; partial sums of
+ * fixed sets of output pixels go to workspace as [splits][cout][cin 49] and a second launch adds them in a fixed order: no
+ * atomics, the same bits on every call.  workspace: cim_conv7x7_dw_workspace(...) bytes, the caller's; cim_conv7x7_dw_splits is a
+ * function of the shape alone.  1 <= cin <= 4, 1 <= cout <= 256, W <= 4096, H W < 2^20; anything else returns -1 before a launch.
+ * Replaces ATen -> MIOpen's convolution weight gradient for that layer. */
+long long cim_conv7x7_dw_workspace(int B, int cin, int cout, int H, int W, int stride);
+int cim_conv7x7_dw_splits(int B, int cin, int cout, int H, int W, int stride);
+int cim_conv7x7_dw_f32(const float* dconv, const float* x, float* dw, int B, int cin, int cout, int H, int W, int stride,
+                       float* workspace, void* stream);
+
 /* ------------------------------------------------------------------ backbone BatchNorm chains (a-11)
  * Frozen-statistics BatchNorm (+ residual) (+ ReLU) of the ResNet / HRNet bodies, lib/modeling/resnet50.py:17-44,53-77
  * (every BN in eval(): running statistics, trainable affine), one launch each way instead of 2-3 / 3-4 ATen passes.
