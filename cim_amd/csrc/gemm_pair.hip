@@ -15,7 +15,8 @@
 //     global_load_lds_dwordx4 (no VGPR round trip, no conversion, no ds_write) and its loop is MFMA + ds_read only.
 // Error: every element carries 22 significant bits relative to ITSELF while |x| >= 2^-13 max|X|, and an absolute error of
 // 2^-39 max|X| below that (fp16 subnormals; MFMA does not flush them): the bound of an fp32 GEMM relative to
-// max|A| max|B| instead of |a_row| |b_col| (tests/test_gpu_gemm.py::test_pair_engine_*).
+// max|A| max|B| instead of |a_row| |b_col| (tests/test_gpu_gemm_pair.py::test_pair_engine_error_class,
+// test_pair_small_elements_keep_absolute_accuracy; exact products at every ragged tile: tests/test_gpu_gemm_pair_abi.py).
 //
 // Tiling: workgroup 256 x 256 x 32, 8 waves as 2 (M) x 4 (N), wave tile 128 x 64 = 4 x 2 MFMA tiles (128 accumulator
 // registers), 48 MFMAs per wave and slab.  Two LDS buffers of 64 KB; ONE barrier per slab, placed between the slab's two
@@ -961,6 +962,8 @@ extern "C" int cim_gemm_pair(const void* A, const void* B, float* C, const float
     CIM_CHECK_ARG(form == 0 || (form == 1 && a_mcontig && !b_kcontig));
     CIM_CHECK_ARG(pair_dims_ok(M, N, K, lda, ldb, ldc, a_mcontig, b_kcontig));
     CIM_CHECK_ARG(splits <= 1 || workspace != nullptr);
+    // more than one split (launch_pair clamps the count to K / 32 slabs): pair_splitk_reduce_kernel moves float4s
+    CIM_CHECK_ARG(splits <= 1 || K <= BK || (((size_t)C | (size_t)workspace | (size_t)bias) & 15) == 0);
     PairArgs g = pair_args(A, B, C, M, N, K, lda, ldb, ldc, a_scale, b_scale);
     g.bias = bias;
     g.relu = relu;

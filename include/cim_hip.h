@@ -793,7 +793,8 @@ int cim_bn_act_bwd(const float* dy, const float* y, const float* x, const float*
  *     K % 32 == 0 (zero-filled rows / columns pad the images), lda / ldb % 8 == 0, an M-contiguous A needs M % 8 == 0, an
  *     N-contiguous B needs N % 8 == 0.  a_scale / b_scale: [batch] device floats, the scales the images were written with.
  *     c_amax (optional): receives max |C| as an IEEE bit pattern through atomicMax (caller zeroes) - the scale source
- *     of the next split.
+ *     of the next split.  With splits > 1 and K > 32 the split-K reduce moves 16 bytes per lane: C, workspace (splits * M * N
+ *     floats) and a non-NULL bias must then be 16-byte aligned (ldc % 4 == 0 always).
  *   cim_pair_scales: scale[i] = 2^(14 - exponent(amax[min(i, n_amax - 1)] * factor[i]))  (factor may be NULL); reduce_all != 0:
  *                    every scale from the MAXIMUM of the n_amax words (row / column maxima of a weight -> its one scale)
  *   cim_pair_split : fp32 X [batch][rows][ld] -> pair image [batch][rows_pad][ldp], rows >= `rows` zero-filled; relu_y
