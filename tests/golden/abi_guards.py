@@ -1,6 +1,7 @@
 """Memory guards of the tests that call the library straight at the C ABI (tests/test_gpu_gemm_small_abi.py,
-tests/test_gpu_gemm_pair_abi.py): operands inside NaN-poisoned memory, outputs inside sentinel memory, a split-K workspace that is NaN
-until it is written, and the bit-for-bit comparison that names the first wrong element."""
+tests/test_gpu_gemm_pair_abi.py, tests/test_gpu_wino7_abi.py): operands inside NaN-poisoned memory, outputs inside sentinel memory,
+pair images a kernel writes inside fp16 NaN, a split-K workspace that is NaN until it is written, and the bit-for-bit comparison
+that names the first wrong element."""
 import torch
 
 NAN = float("nan")
@@ -19,6 +20,39 @@ def _poisoned(t, pad=0):
     v.copy_(t)
     assert v.data_ptr() % 8 == 4
     return v, ld
+
+
+def _poisoned16(t):
+    """The values of the dense tensor `t` (any shape) inside a NaN-filled buffer, 64 NaN floats on either side, the first element
+    16-byte aligned: for the kernels that read their operand as float4.  -> the view"""
+    buf = torch.full((GUARD + t.numel() + GUARD,), NAN, dtype=torch.float32, device=t.device)
+    v = buf[GUARD:GUARD + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == 0
+    return v
+
+
+F16_NAN2 = 0x7E007E00        # two fp16 quiet NaNs: what every int32 of a pair-image buffer holds before a call
+
+
+class _ImageOut:
+    """A pair image of n int32 that a kernel is to write, 32-byte aligned, preset to fp16 NaN like the 64 int32 on either side."""
+
+    def __init__(self, n, dev):
+        self.n = n
+        self.raw = torch.full((GUARD + n + GUARD,), F16_NAN2, dtype=torch.int32, device=dev)
+        self.ptr = self.raw.data_ptr() + 4 * GUARD
+        assert self.ptr % 32 == 0
+
+    def check(self):
+        """Everything outside the n words unchanged, every word inside written. -> the image, int32 [n] on the host"""
+        raw = self.raw.cpu().numpy()
+        out = (raw[:GUARD] != F16_NAN2).sum() + (raw[GUARD + self.n:] != F16_NAN2).sum()
+        assert out == 0, "a store outside the image: %d int32 changed" % int(out)
+        img = raw[GUARD:GUARD + self.n]
+        left = int((img == F16_NAN2).sum())
+        assert left == 0, "%d int32 of the image were not written, the first at %d" % (left, int((img == F16_NAN2).argmax()))
+        return img
 
 
 class _Out:
