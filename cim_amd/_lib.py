@@ -65,7 +65,7 @@ VALUE_RETURNING = {name for name, (restype, _) in FUNCTIONS.items() if restype i
 # split counts / workspace sizes of the body's layers: pure functions of their integer arguments (their tuning switches are read
 # once per process), asked ~100 times per training step with the step's few dozen layer shapes
 PURE = {"cim_maxpool2d_out_size", "cim_conv3x3_dx_parts", "cim_gemm_small_splits", "cim_conv3x3_nchw_splits", "cim_conv1x1_bwd_workspace", "cim_conv3x3_nchw_bwd_workspace",
-        "cim_bn_act_bwd_chunks", "cim_gemm_pair_splits"}
+        "cim_bn_act_bwd_chunks", "cim_gemm_pair_splits", "cim_bn_train_workspace"}
 _PURE_VALUES = {}
 
 

@@ -5,6 +5,7 @@ names the reference re-exports are kept importable and raise if called (RoIPool 
 only through ROI_XFORM_METHOD=RoIPoolF, which no shipped config sets; nms / soft_nms are
 eval-only box ops) - SURVEY.md section 2.2."""
 from .bn_act import bn_act
+from .bn_train import bn_act_train
 from .conv1x1 import conv1x1_bn_act
 from .conv3x3 import conv3x3_bias_act, conv3x3_bn_act, conv7x7_bn_act, conv7x7_bn_act_train
 from .pool import max_pool2d, upsample_nearest
@@ -27,4 +28,4 @@ roi_pool = _out_of_scope("roi_pool")
 nms = _out_of_scope("nms")
 soft_nms = _out_of_scope("soft_nms")
 
-__all__ = ["RoIPool", "RoIAlign", "roi_pool", "roi_align", "nms", "soft_nms", "roi_align_maskcat", "bn_act", "conv1x1_bn_act", "conv3x3_bn_act", "conv3x3_bias_act", "conv7x7_bn_act", "conv7x7_bn_act_train", "max_pool2d", "upsample_nearest"]
+__all__ = ["RoIPool", "RoIAlign", "roi_pool", "roi_align", "nms", "soft_nms", "roi_align_maskcat", "bn_act", "bn_act_train", "conv1x1_bn_act", "conv3x3_bn_act", "conv3x3_bias_act", "conv7x7_bn_act", "conv7x7_bn_act_train", "max_pool2d", "upsample_nearest"]

@@ -13,7 +13,10 @@ detector's body trains on.
     loss.backward()
 
 `cim_amd.prm.PeakResponseMapping` itself stays the inference object (its train() raises, its forward runs under no_grad): a
-checkpoint moves between the two entries unchanged.  BatchNorm statistics stay frozen (the reference's train() updates them).
+checkpoint moves between the two entries unchanged.  By default BatchNorm statistics stay frozen; `batch_stats=True` (on
+`class_response_maps`, `aggregate` and `loss`) runs every BatchNorm of a stage that trains on the statistics of the batch and
+updates its running buffers, as the reference's train() does (`ops.bn_act_train`): with `unfreeze` +
+`batch_stats=True` the step is lib/prm/prm_model.py's, nothing left out.
 A stem that trains takes `ops.conv7x7_bn_act_train` (the 7 x 7 weight gradient of csrc/conv7x7_dw.hip).
 Takes DEVICE tensors; a CPU tensor is an error (no CPU fallback)."""
 import numpy as np
@@ -22,7 +25,9 @@ from torch.autograd import Function
 
 from . import _lib
 from . import prm as _prm
-from .ops import conv1x1_bn_act, conv7x7_bn_act, conv7x7_bn_act_train, max_pool2d
+from .modeling.resnet50 import Bottleneck
+from .ops import bn_act_train, conv1x1_bn_act, conv3x3_bn_act, conv7x7_bn_act, conv7x7_bn_act_train, max_pool2d
+from .ops.conv3x3 import Conv7x7Function
 
 STIM_MAX_HW = _lib.CONSTANTS["CIM_PRM_STIM_MAX_HW"]
 STATUS_NAN, STATUS_NO_PEAK = _prm.STATUS_NAN, _prm.STATUS_NO_PEAK
@@ -151,7 +156,8 @@ def freeze(model, at=2):
 
 def unfreeze(model):
     """requires_grad = True on EVERY parameter of the PeakResponseMapping `model`: the reference's training state
-    (lib/prm/prm_model.py trains every layer).  BatchNorm statistics still stay frozen."""
+    (lib/prm/prm_model.py trains every layer).  BatchNorm statistics stay frozen unless the step asks for `batch_stats=True`;
+    with both, the stated difference from lib/prm/prm_model.py's train() is gone."""
     _features(model)
     for p in model.parameters():
         p.requires_grad = True
@@ -177,28 +183,81 @@ def _identity_bn(device, c):
     return _IDENTITY_BN[key]
 
 
-def class_response_maps(model, images):
+def _bare(wrapper, x, conv):
+    """conv(x) alone on the fused launch: the identity BatchNorm, no ReLU (as the classifier below)."""
+    return wrapper(x, conv, _identity_bn(x.device, conv.out_channels), relu=False)
+
+
+def _stem_batch_stats(images, conv, bn):
+    """relu(bn(conv(images))) with batch statistics: the bare 7 x 7 launch (its weight gradient: csrc/conv7x7_dw.hip), then
+    `bn_act_train`."""
+    if not (conv.kernel_size == (7, 7) and conv.padding == (3, 3) and conv.stride in ((1, 1), (2, 2)) and conv.dilation == (1, 1)
+            and conv.groups == 1 and conv.bias is None and 1 <= conv.in_channels <= 4 and 1 <= conv.out_channels <= 256
+            and images.shape[3] <= 4096 and images.shape[2] * images.shape[3] < (1 << 20)):
+        raise ValueError("cim_amd.prm_train: unsupported stem %s on an input of shape %s" % (conv, tuple(images.shape)))
+    if torch.is_grad_enabled() and images.requires_grad:
+        raise ValueError("cim_amd.prm_train: the images require a gradient: the stem's data gradient is not built")
+    args = (images.contiguous(), conv.weight if conv.weight.is_contiguous() else conv.weight.contiguous(), conv.stride[0])
+    if torch.is_grad_enabled() and conv.weight.requires_grad:
+        z = Conv7x7Function.apply(*args)
+    else:
+        with torch.no_grad():
+            z = Conv7x7Function.apply(*args)
+    return bn_act_train(z, bn, relu=True)
+
+
+def _bottleneck_batch_stats(block, x):
+    """modeling/resnet50.py Bottleneck.forward with every BatchNorm on batch statistics: each convolution bare on its fused launch,
+    `bn_act_train` behind it with the block's residual and ReLU."""
+    out = bn_act_train(_bare(conv1x1_bn_act, x, block.conv1), block.bn1)
+    out = bn_act_train(_bare(conv3x3_bn_act, out, block.conv2), block.bn2)
+    identity = x
+    if block.downsample is not None:
+        identity = bn_act_train(_bare(conv1x1_bn_act, x, block.downsample[0]), block.downsample[1], relu=False)
+    return bn_act_train(_bare(conv1x1_bn_act, out, block.conv3), block.bn3, residual=identity, relu=True)
+
+
+def _trains(*modules):
+    return any(p.requires_grad for m in modules for p in m.parameters())
+
+
+def class_response_maps(model, images, batch_stats=False):
     """model[0] under the current grad mode: the stem (one fused launch when frozen, its training form when one of its parameters
     requires a gradient), layer1..layer4 and the 1 x 1 classifier on the fused launches, the classifier WITH autograd - its
     convolution bias folded into the identity BatchNorm's mean (ops/conv1x1.py), its weight and bias gradients from the small-tile
-    GEMM path."""
+    GEMM path.
+
+    batch_stats=True: a stage of `features` (the stem; layer1 .. layer4) with at least one parameter that requires a gradient runs
+    every BatchNorm on the statistics of the batch and updates its running buffers, as lib/prm/prm_model.py's train() does - each
+    convolution bare on its fused launch, `ops.bn_act_train` behind it.  A stage with nothing to train (after `freeze`) keeps its
+    module call and its running statistics.  After `unfreeze` this is the reference's training forward."""
     f = _features(model)
-    trains = torch.is_grad_enabled() and any(p.requires_grad for i in range(4) for p in f[i].parameters())
-    x = max_pool2d((conv7x7_bn_act_train if trains else conv7x7_bn_act)(images, f[0], f[1], relu=True), f[3])
+    if batch_stats and _trains(f[0], f[1]):
+        x = max_pool2d(_stem_batch_stats(images, f[0], f[1]), f[3])
+    else:
+        trains = torch.is_grad_enabled() and any(p.requires_grad for i in range(4) for p in f[i].parameters())
+        x = max_pool2d((conv7x7_bn_act_train if trains else conv7x7_bn_act)(images, f[0], f[1], relu=True), f[3])
     for i in range(4, 8):
-        x = f[i](x)
+        if batch_stats and _trains(f[i]):
+            for block in f[i]:
+                if not isinstance(block, Bottleneck):
+                    raise TypeError("cim_amd.prm_train: batch_stats=True walks cim_amd.modeling.resnet50.Bottleneck blocks, got %r" % (type(block),))
+                x = _bottleneck_batch_stats(block, x)
+        else:
+            x = f[i](x)
     conv = model[0].classifier[0]
     return conv1x1_bn_act(x, conv, _identity_bn(x.device, conv.out_channels), relu=False)
 
 
-def aggregate(model, images):
+def aggregate(model, images, batch_stats=False):
     """images [B,3,S,S'] normalised fp32 on the device -> (aggregation [B,C], state): class_response_maps, then peak_stimulation
-    at the model's sub_pixel_locating_factor."""
+    at the model's sub_pixel_locating_factor.  batch_stats: see `class_response_maps`."""
     _device_f32(images, "aggregate", "images", 4)
-    return peak_stimulation(class_response_maps(model, images), int(model.sub_pixel_locating_factor))
+    return peak_stimulation(class_response_maps(model, images, batch_stats=batch_stats), int(model.sub_pixel_locating_factor))
 
 
-def loss(model, images, target):
-    """The PRM classification loss of a batch: `aggregate`, then `multilabel_soft_margin_loss` against target [B,C]."""
-    agg, _ = aggregate(model, images)
+def loss(model, images, target, batch_stats=False):
+    """The PRM classification loss of a batch: `aggregate`, then `multilabel_soft_margin_loss` against target [B,C].  With
+    `unfreeze(model)` and batch_stats=True this is the training step of lib/prm/prm_model.py, BatchNorm statistics included."""
+    agg, _ = aggregate(model, images, batch_stats=batch_stats)
     return multilabel_soft_margin_loss(agg, target)

@@ -775,6 +775,30 @@ int cim_bn_act_bwd(const float* dy, const float* y, const float* x, const float*
                    const float* var, float eps, float* dx, float* dres, float* dgamma, float* dbeta,
                    int N, int C, int HW, int relu, void* stream);
 
+/* Batch-statistics BatchNorm (+ residual) (+ ReLU): nn.BatchNorm2d in train() mode (csrc/bn_train.hip; ABI-16 addition:
+ * cim_abi_version() stays 16).  What lib/prm/prm_model.py's PeakResponseMapping.train() runs in every BatchNorm of its network.
+ * Layout as above, m = N HW values per channel.  A channel's values are cut into cim_bn_train_chunks(N,C,HW) chunks, a function of
+ * the shape alone; per-chunk partials go to workspace (cim_bn_train_workspace(N,C,HW) bytes, the caller's, 8-byte aligned, the same
+ * size for both calls) and a finishing launch adds them in a fixed order, in double: no atomics, the same bits on every call.
+ *   fwd: mean, var (biased; centred sums joined with Chan's formula) and, when rstd != NULL, rstd = rsqrtf(var + eps) are WRITTEN;
+ *        y = cim_bn_act_fwd(x, res, gamma, beta, mean, var, eps), bit for bit (it is that call).  With running_mean / running_var
+ *        (both or neither):  running_mean = (1 - f) running_mean + f mean,  running_var = (1 - f) running_var + f var m / (m - 1),
+ *        f = momentum, or, momentum < 0 (torch's momentum None), 1 / *num_batches_tracked AFTER its increment.
+ *        *num_batches_tracked (int64 device word, may be NULL unless momentum < 0 with running buffers) += 1, an ordinary store.
+ *   bwd (sums and dx computed in double): dz = dy*(y>0 if relu);  S1 = sum dz, S2 = sum dz (x - mean);  dbeta = S1, dgamma = rstd S2 (both or neither);
+ *        dx = gamma rstd (dz - S1 / m - (x - mean) rstd^2 S2 / m), dres = dz (each may be NULL); y may be NULL without relu.
+ * 16-byte accesses when every tensor's base is 16-byte aligned, else scalar ones.  C < 1, N HW < 2 (torch: "Expected more than 1
+ * value per channel when training"), N C HW > INT_MAX or a NULL required pointer return -1 before any launch; the two size
+ * entries return -1 for such a shape. */
+long long cim_bn_train_workspace(int N, int C, int HW);
+long long cim_bn_train_chunks(int N, int C, int HW);
+int cim_bn_train_fwd(const float* x, const float* res, const float* gamma, const float* beta, float eps, float momentum,
+                     float* running_mean, float* running_var, long long* num_batches_tracked, float* y, float* mean, float* var,
+                     float* rstd, int N, int C, int HW, int relu, float* workspace, void* stream);
+int cim_bn_train_bwd(const float* dy, const float* y, const float* x, const float* gamma, const float* mean, const float* rstd,
+                     float* dx, float* dres, float* dgamma, float* dbeta, int N, int C, int HW, int relu, float* workspace,
+                     void* stream);
+
 /* ------------------------------------------------------------------ MaskFuse contractions (a-2)
  * The dense contractions behind MaskFuse, lib/modeling/resnet50.py:104-110,135-136 (Conv2d(2C,C,3,pad=1) in the mixed 4 + 3
  * Winograd tiling of the 7 x 7 ROI map, Linear(49C,4096), Linear(4096,4096)) and their autograd backward: fp32 in, fp32 out, on
