@@ -1,7 +1,8 @@
 """Memory guards of the tests that call the library straight at the C ABI (tests/test_gpu_gemm_small_abi.py,
-tests/test_gpu_gemm_pair_abi.py, tests/test_gpu_wino7_abi.py): operands inside NaN-poisoned memory, outputs inside sentinel memory,
-pair images a kernel writes inside fp16 NaN, a split-K workspace that is NaN until it is written, and the bit-for-bit comparison
-that names the first wrong element."""
+tests/test_gpu_gemm_pair_abi.py, tests/test_gpu_wino7_abi.py, tests/test_gpu_mask_iou_abi.py, tests/test_gpu_image_prep_abi.py,
+tests/test_gpu_pool.py): operands inside NaN-poisoned memory, outputs inside sentinel memory, pair images a kernel writes inside
+fp16 NaN, a split-K workspace that is NaN until it is written, the bit-for-bit comparison that names the first wrong element, and
+the integer variants: byte operands inside 0xFF, integer results inside a sentinel of their type."""
 import torch
 
 NAN = float("nan")
@@ -68,10 +69,14 @@ class _Out:
         self.ptr = self.view.data_ptr()
         assert self.raw.data_ptr() % 16 == 0 and self.ptr % 16 == 4 * shift
 
-    def check(self):
-        """Everything inside [M][N] finite, everything outside untouched (compared as int32). -> the dense result"""
+    def check(self, finite=True):
+        """Everything inside [M][N] finite (finite = False: merely no longer the sentinel's bits, for results that may be
+        infinite), everything outside untouched (compared as int32). -> the dense result"""
         got = self.view.clone()
-        assert bool(torch.isfinite(got).all()), "an element of the result was not written (or is not finite)"
+        if finite:
+            assert bool(torch.isfinite(got).all()), "an element of the result was not written (or is not finite)"
+        else:
+            assert bool((got.view(torch.int32) != SENT).all()), "an element of the result was not written"
         rest = self.raw.clone()
         rest.as_strided((self.M, self.N), (self.ld, 1), self.front).fill_(SENT)
         assert bool((rest == SENT).all()), "a store outside [M][N]: %d floats changed" % int((rest != SENT).sum())
@@ -102,3 +107,66 @@ def _same(got, want, what):
         first = bad.nonzero()[0].tolist()
         raise AssertionError("%s: %d of %d elements differ, first at %s: got %r, want %r"
                              % (what, int(bad.sum()), bad.numel(), first, float(got[tuple(first)]), float(want[tuple(first)])))
+
+
+# ---- integer buffers: masks and images (uint8), half maps as their bits (uint16), areas and arg-max (int32), packed words (int64) ----
+
+SENT_U8 = 0xFF               # the byte poison: a read past a mask's row or past the last mask turns bits ON
+SENT_U16 = 0x7BFF            # 65504, the largest finite half: no ratio of two counts and not a NaN
+SENT_I32 = -0x41105EA1       # no count and no arg-max is negative
+SENT_I64 = 0x5EA15EA15EA15EA1
+_INT_SENT = {torch.uint8: SENT_U8, torch.int16: SENT_U16, torch.int32: SENT_I32, torch.int64: SENT_I64}
+
+
+class _OutInt:
+    """_Out for integer results: [M][N] of `dtype` (uint8, int16 for the bits of a uint16, int32, int64) with leading dimension
+    N + pad, two guard rows + 64 elements on either side, every element preset to the dtype's sentinel above."""
+
+    def __init__(self, M, N, pad, dev, dtype):
+        self.M, self.N, self.ld, self.sent = M, N, N + pad, _INT_SENT[dtype]
+        self.front = (2 * self.ld + GUARD + 15) // 16 * 16
+        total = self.front + M * self.ld + 2 * self.ld + GUARD
+        self.raw = torch.full((total,), self.sent, dtype=dtype, device=dev)
+        self.view = self.raw.as_strided((M, N), (self.ld, 1), self.front)
+        self.ptr = self.view.data_ptr()
+        assert self.ptr % 16 == 0
+
+    def untouched(self):
+        return bool((self.raw == self.sent).all())
+
+    def check(self):
+        """Every element inside [M][N] written (no longer the sentinel), everything outside untouched. -> the dense result"""
+        got = self.view.clone()
+        left = int((got == self.sent).sum())
+        assert left == 0, "%d elements of the result were not written, the first at %s" % (left, (got == self.sent).nonzero()[0].tolist())
+        rest = self.raw.clone()
+        rest.as_strided((self.M, self.N), (self.ld, 1), self.front).fill_(self.sent)
+        assert bool((rest == self.sent).all()), "a store outside [M][N]: %d elements changed" % int((rest != self.sent).sum())
+        return got
+
+
+def _poisoned_u8(t, shift=0, front=None, back=None):
+    """The bytes of the dense uint8 tensor `t` inside a poisoned buffer, 64 + shift bytes in front (shift = 0: the first byte is
+    16-byte aligned; 1: aligned to nothing) and 64 behind.  The poison is 0xFF, or the byte patterns `front` / `back` (uint8
+    tensors that are repeated towards the outside, front's last byte lying just before the data).  -> the view"""
+    n = t.numel()
+    lead = GUARD + shift
+    buf = torch.full((lead + n + GUARD,), SENT_U8, dtype=torch.uint8, device=t.device)
+    if front is not None:
+        reps = (lead + front.numel() - 1) // front.numel()
+        buf[:lead] = front.repeat(reps)[-lead:]
+    if back is not None:
+        buf[lead + n:] = back.repeat((GUARD + back.numel() - 1) // back.numel())[:GUARD]
+    v = buf[lead:lead + n].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == shift
+    return v
+
+
+def _poisoned_i64(t):
+    """The values of the dense int64 tensor `t` with 64 words of all-ones on either side (a read past the packed masks adds set
+    bits to a count).  -> the view"""
+    buf = torch.full((GUARD + t.numel() + GUARD,), -1, dtype=torch.int64, device=t.device)
+    v = buf[GUARD:GUARD + t.numel()].view(t.shape)
+    v.copy_(t)
+    return v
