@@ -7,13 +7,14 @@ names (`mask_branch.0`, `seg_fc.0`, `seg_fc.2`) and the same (c, h, w) flatten o
 
 MI355X design: the ROIAlign output, the mask product and the channel concat are produced by
 ONE fused HIP kernel straight into the conv input (channels-last), instead of three
-materialised tensors (box_x, mask_x, cat) as in the reference.
+materialised tensors (box_x, mask_x, cat) as in the reference.  Under FAST_RCNN.ROI_XFORM_METHOD = RoIPoolF the pooling
+is RoIPool (ops/roi_pool.py), fused with the mask product and the concat in the same way.
 """
 import torch
 import torch.nn as nn
 
 from ..core.config import cfg
-from ..ops import maskfuse_pair, pair, roi_align_maskcat
+from ..ops import maskfuse_pair, pair, roi_align_maskcat, roi_pool_maskcat
 
 
 # The box head as ONE autograd node whose first launch writes the convolution's Winograd input image straight from the feature map
@@ -47,7 +48,8 @@ class MaskFuse(nn.Module):
     @staticmethod
     def _cat_amax(x, masks):
         """int32[2] bit patterns (max |x|, max |mask|): the scale source of the convolution's input image.  ROIAlign averages feature
-        pixels and the masks multiply them: max |cat| <= max |x| max(1, max |mask|) - two small passes instead of one over cat."""
+        pixels, RoIPool takes the maximum of some or 0 - either way |box_x| <= max |x| - and the masks multiply them:
+        max |cat| <= max |x| max(1, max |mask|) - two small passes instead of one over cat."""
         xd, md = x.detach(), masks.detach().to(torch.float32)
         if not (xd.is_contiguous() or xd.is_contiguous(memory_format=torch.channels_last)):
             xd = xd.contiguous()
@@ -58,12 +60,16 @@ class MaskFuse(nn.Module):
 
     def forward(self, x, rois, masks):
         method = cfg.FAST_RCNN.ROI_XFORM_METHOD
-        if method != "RoIAlign":
-            raise NotImplementedError("MaskFuse: only ROI_XFORM_METHOD=RoIAlign is on the CIM path (got %s)" % method)
+        if method not in ("RoIAlign", "RoIPoolF"):      # (RoICrop has no implementation in the reference either: model_builder.py:224-231)
+            raise NotImplementedError("MaskFuse: ROI_XFORM_METHOD=%s has no implementation on the CIM path" % method)
         # the nn.Conv2d / nn.Linear modules only hold the parameters (reference names and layouts)
         conv = self.mask_branch[0]
         fc1, fc2 = self.seg_fc[0], self.seg_fc[2]
         res, sr = cfg.FAST_RCNN.ROI_XFORM_RESOLUTION, cfg.FAST_RCNN.ROI_XFORM_SAMPLING_RATIO
+        if method == "RoIPoolF":
+            # two launches: RoIPool + mask multiply + concat (`cat` stored), then the head.  A cat value is a feature pixel or 0 where
+            # ROIAlign's is an average of pixels, so the bound of _cat_amax holds unchanged
+            return self._head(roi_pool_maskcat(x, rois, masks, res, self.spatial_scale), x, masks)
         import sys
         if (FUSE_ROI_WINO and not sys.modules["cim_amd.ops.roi_align"].EXACT
                 and maskfuse_pair.roi_supported(x, conv.weight, fc1.weight, fc2.weight, res)):
@@ -79,7 +85,12 @@ class MaskFuse(nn.Module):
             logging.getLogger("cim_amd.maskfuse").warning(
                 "feature map %d x %d exceeds the fused ROIAlign -> Winograd launch's 128 x 128 table limit: the two-launch path "
                 "(roi_align_maskcat + wino7_input_pair, `cat` materialised) runs for such images", x.shape[2], x.shape[3])
-        cat = roi_align_maskcat(x, rois, masks, res, self.spatial_scale, sr, aligned=True)
+        return self._head(roi_align_maskcat(x, rois, masks, res, self.spatial_scale, sr, aligned=True), x, masks)
+
+    def _head(self, cat, x, masks):
+        """conv -> flatten -> fc1 -> fc2 behind a stored `cat` (the two-launch shape of either pooling method)."""
+        conv = self.mask_branch[0]
+        fc1, fc2 = self.seg_fc[0], self.seg_fc[2]
         if not maskfuse_pair.supported(cat, conv.weight, fc1.weight, fc2.weight):
             # ONE engine, ONE algorithm: every configuration of the reference (512 / 1024 / 2048 feature channels, 7 x 7 ROI maps,
             # 4096-wide fully connected layers) qualifies; anything else fails loudly instead of taking a second code path
@@ -87,6 +98,6 @@ class MaskFuse(nn.Module):
                 "MaskFuse: the MI355X contraction engine takes 7 x 7 ROI maps, dim_in a multiple of 16 (conv output channels a multiple "
                 "of 64) and fully connected widths that are multiples of 32 - got cat %s, conv %s, fc %s / %s"
                 % (tuple(cat.shape), tuple(conv.weight.shape), tuple(fc1.weight.shape), tuple(fc2.weight.shape)))
-        # conv -> flatten -> fc1 -> fc2 on pair images (one scale per matrix).  ROIAlign averages feature pixels and the masks are
-        # {0, 1}: max |cat| <= max |x| max(1, max |mask|) - a 6 MB pass instead of one over cat
+        # conv -> flatten -> fc1 -> fc2 on pair images (one scale per matrix).  ROIAlign averages feature pixels, RoIPool picks one
+        # (or 0), and the masks are {0, 1}: max |cat| <= max |x| max(1, max |mask|) - a 6 MB pass instead of one over cat
         return maskfuse_pair.maskfuse_head(cat, conv, fc1, fc2, self._cat_amax(x, masks))

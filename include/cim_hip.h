@@ -130,6 +130,50 @@ int cim_roi_align_maskcat_bwd(const float* grad_cat, const float* rois, const fl
 int cim_roi_align_forms(int B, int C, int H, int W, int K, int P, int maskcat, int has_workspace, int tables_ready,
                         int* fwd_form, int* bwd_form, int* bwd_builds_tables);
 
+/* ------------------------------------------------------------------ RoIPool (FAST_RCNN.ROI_XFORM_METHOD = RoIPoolF)
+ * Replaces mmcv.ops.RoIPool(output_size=P, spatial_scale) as imported by lib/ops/__init__.py:6 and called at
+ * lib/modeling/model_builder.py:227-228, and - the mask-cat forms - the prologue of MaskFuse.forward behind it
+ * (lib/modeling/resnet50.py:131-134).  csrc/roi_pool.hip; DESIGN.md 4.24.  Additive: cim_abi_version() stays 16.
+ *
+ * Channels-last like ROIAlign: feat [B,H,W,C] f32, rois [K,5] f32 = (batch, x1, y1, x2, y2), out [K,P,P,C] f32,
+ * cat [K,P,P,2C] f32, masks [K,P,P] f32, argmax [K,P,P,C] int32.
+ *
+ * The contract (tests/golden/roi_pool_np.py restates it float for float; out and argmax are bit-identical to it).  All in
+ * fp32, every operation rounded separately - no FMA contraction, a correctly rounded division, no reciprocal:
+ *   b   = (int) rois[k][0]
+ *   rx1 = x1 * s;  ry1 = y1 * s;  rx2 = (x2 + 1) * s;  ry2 = (y2 + 1) * s;  rw = rx2 - rx1;  rh = ry2 - ry1
+ *   rw <= 0 or rh <= 0:  every output of the ROI is 0 and every argmax -1
+ *   bw = rw / P;  bh = rh / P
+ *   bin (ph, pw):  x in [floor(pw * bw + rx1), ceil((pw + 1) * bw + rx1)),  y in [floor(ph * bh + ry1), ceil((ph + 1) * bh + ry1)),
+ *                  each bound clamped to [0, W] / [0, H]
+ *   empty bin (y_hi <= y_lo or x_hi <= x_lo):  value 0, argmax -1
+ *   else  v = -FLT_MAX, idx = -1;  y ascending, then x ascending:  if feat[b,y,x,c] > v then v = that pixel, idx = y * W + x
+ * The strict > sends ties to the first pixel in row-major order and never selects NaN; a bin whose pixels are all -inf or
+ * NaN yields -FLT_MAX with argmax -1.  argmax == NULL (inference) stores no indices.  The mask-cat forward writes
+ * cat[..., :C] = v and cat[..., C:] = fl(v * masks[k,ph,pw]) in the same launch.
+ *
+ * Backward: grad_in[b, idx, c] += grad_out[k,ph,pw,c] for every argmax idx != -1 (mask-cat: += fl(dlo + fl(mask * dhi))), nothing
+ * else; every element of grad_in is written (zero where nothing lands).  It takes rois and spatial_scale besides argmax: the
+ * image of ROI k is rois[k][0], and the bins' bounds tell a workgroup which bins can reach its pixels.  argmax must be what the
+ * forward wrote for these rois and this scale: an index outside its own bin's bounds is left out, never stored out of range.
+ * No float atomics; per destination the terms are added in ascending (k, ph, pw) inside a group of ROIs and the groups in
+ * order: two calls give the same bits.  scratch: cim_roi_pool_bwd_scratch(K,B,C,H,W,P) bytes for the groups' partial maps
+ * (0: one group, scratch may be NULL), the caller's, 16-byte aligned for the 16-byte form of the sum; P does not enter today.
+ *
+ * Refused (-1, before any device work): a null pointer (except argmax in the forward, scratch where 0 bytes are asked for, and
+ * the per-ROI arrays when K == 0), B, C, H, W or P below 1, K < 0, H W >= 2^31, K P P C (mask-cat: K P P 2C) >= 2^31.  K == 0
+ * succeeds: the forward writes nothing, the backward an all-zero grad_in.  NOT checked: a batch index outside [0, B) is the
+ * caller's error and no refusal - such a ROI comes out as a malformed one and receives no gradient.  Re-entrant: no state, caller's stream and scratch. */
+int cim_roi_pool_fwd(const float* feat, const float* rois, float* out, int* argmax,
+                     int B, int C, int H, int W, int K, int P, float spatial_scale, void* stream);
+int cim_roi_pool_maskcat_fwd(const float* feat, const float* rois, const float* masks, float* cat, int* argmax,
+                             int B, int C, int H, int W, int K, int P, float spatial_scale, void* stream);
+long long cim_roi_pool_bwd_scratch(int K, int B, int C, int H, int W, int P);
+int cim_roi_pool_bwd(const float* grad_out, const float* rois, const int* argmax, float* grad_in,
+                     int B, int C, int H, int W, int K, int P, float spatial_scale, float* scratch, void* stream);
+int cim_roi_pool_maskcat_bwd(const float* grad_cat, const float* rois, const float* masks, const int* argmax, float* grad_in,
+                             int B, int C, int H, int W, int K, int P, float spatial_scale, float* scratch, void* stream);
+
 /* ------------------------------------------------------------------ mask IoU / containment maps (a-7)
  * Replaces lib/utils/mask_utils.py:6-18 (mask_iou) and :20-32 (mask_asymmetric_iou) as driven
  * by tools/pre/create_cob_iou.py:43-49 / create_cob_asy_iou.py:43-53, and the per-step
