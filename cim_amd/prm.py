@@ -5,11 +5,13 @@ lib/prm/prm_modules.py (`PeakStimulation`): ONE forward pass of a frozen-BatchNo
 convolution + BatchNorm (+ residual) (+ ReLU) one launch of the kernels the detector's body runs on - and three launches of
 csrc/prm.hip (bilinear up-sampling, median-filtered peaks, ascending-score order) for a BATCH of images.  The reference also
 back-propagates every valid peak through the network (the peak response maps); the label assignment reads only their number,
-which is the number of valid peaks, so that pass is not reproduced.
+which is the number of valid peaks, so `peaks` does not run that pass.  `backprop` and `peak_response_maps` (prm_backprop.py,
+DESIGN.md 4.25) do: one backward walk whose batch dimension is the peaks.
 
     model = PeakResponseMapping(fc_resnet50(num_classes=20))          # state_dict keys of the reference: prm_voc.pth loads
     model.load_state_dict(torch.load("prm_voc.pth", map_location="cpu"), strict=True)
     rows, cols, classes, scores = peaks(model.cuda(), images, labels)[0]
+    rows, cols, classes, scores, maps = peak_response_maps(model, images, labels)[0]     # + the peak response maps [P, S, S']
 
 Takes DEVICE tensors; a CPU tensor is an error in `peaks` (no CPU fallback).  The modules themselves run on CPU tensors through
 the ATen branch of the wrappers (host-side tests of the architecture)."""
@@ -144,10 +146,12 @@ class PeakResponseMapping(nn.Sequential):
             return super().forward(input)
 
     def instance_seg(self, *a, **k):
-        raise _not_here("instance_seg (the peak back-propagation)")
+        raise _not_here("instance_seg (the proposal retrieval behind the peak response maps; the maps themselves: "
+                        "cim_amd.prm.peak_response_maps)")
 
     def instance_nms(self, *a, **k):
-        raise _not_here("instance_nms (the peak back-propagation)")
+        raise _not_here("instance_nms (the proposal retrieval behind the peak response maps; the maps themselves: "
+                        "cim_amd.prm.peak_response_maps)")
 
 
 def peak_response_mapping(backbone=None, win_size=3, sub_pixel_locating_factor=8, filter_type="median", **kargs):
@@ -346,3 +350,6 @@ def peaks(model, images, labels, peak_threshold=10, image_sizes=None, details=Fa
         raise _lib.CimHipError("cim_amd.prm.peaks: CUDA/HIP tensor expected (no CPU fallback)")
     crm = model(images)
     return peaks_from_crm(crm, labels, int(model.sub_pixel_locating_factor), image_sizes, peak_threshold, details)
+
+
+from .prm_backprop import backprop, peak_response_maps  # noqa: E402,F401  (the peak back-propagation: prm_backprop.py)

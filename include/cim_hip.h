@@ -622,6 +622,49 @@ int cim_prmt_stim_backward(const float* grad_agg, const int32_t* count, const ui
                            int factor, float* dcrm, float* dbias, void* stream);
 int cim_prmt_msm_loss(const float* agg, const float* target, int B, int C, float* loss, float* dagg, void* stream);
 
+/* ------------------------------------------------------------------ PRM peak back-propagation: the peak response maps (ABI-16 addition)
+ * Replaces what PeakResponseMapping(...).inference() does behind its forward pass (lib/prm/prm_model_gt.py:249-310): every valid
+ * peak sent back through convolutions patched by lib/prm/prm_modules.py:104-140 (pr_conv2d: offset o = min x, xs = x - o,
+ * n = conv(xs, max(W, 0)), ghat = n < 1e-10 ? 0 : g / (|n| + 1e-10), dx = xs * conv_transpose(ghat, max(W, 0))), P sequential
+ * batch-1 passes there; here ONE pass whose batch dimension is the P peaks over tensors of the forward pass that all peaks share.
+ * The products are cim_conv1x1_bn_act_bwd / cim_conv3x3_nchw_bn_act_bwd with w = max(W, 0), dy_is_dconv = 1, dw = NULL, B = P;
+ * these entries are the stages between them and the stem's data gradient (csrc/prm_backprop.hip).  Stateless, re-entrant on the
+ * caller's stream, no atomics, every sum in a fixed order.  Additive: cim_abi_version() stays 16, no new struct.  The entries are
+ * named cim_prmb_*: "PRM back-propagation".  Exactness contract and the bytes each launch moves: DESIGN.md 4.25.
+ * Every entry refuses (-1, cim_last_error() names the condition) a NULL pointer that is not marked optional and a count < 1.
+ *
+ * cim_prmb_min: out[0] = the minimum of x[0..n) (NaN is skipped), no host read.  part: cim_prmb_min_parts(n) floats of scratch
+ *   (at most CIM_PRMB_MIN_MAX_PARTS).  Two launches.
+ * cim_prmb_shift: xs[i] = x[i] - o[0], o a device scalar.  n < 2^31.
+ * cim_prmb_gate: g [P, C, HW], and of ONE image: mul [C, HW] (or NULL: the xs of the convolution that produced g as its raw data
+ *   gradient; g is taken as mul * g), y [C, HW] (or NULL: no ReLU), a [C] (or NULL: no BatchNorm; a = gamma rsqrt(var + eps), its
+ *   sign kept), n [C, HW] ->
+ *     t = y > 0 ? g : 0;   dres [P, C, HW] (or NULL) = t;   dconv [P, C, HW] = n < 1e-10 ? 0 : (t * a) / (|n| + 1e-10).
+ *   mul, y, a and n are read once per launch, not once per peak.  C HW < 2^31.
+ * cim_prmb_scale: dx [P, n] = xs [n] * dxraw [P, n] (+ add [P, n] when given: the gradient that reaches x through another branch).
+ * cim_prmb_seed: peaks [P, 3] int32 in DEVICE memory = (class, y, x) on the up-sampled grid (factor h x factor w) ->
+ *   dconv [P, C, h, w] of the classifier: the one-hot seed through the adjoint of cim_prm_upsample's own taps (its fp32 weights;
+ *   the four products lx ly are added to their tap pixels in the order 00, 01, 10, 11, coinciding taps add up), then the gate
+ *   with n [C, h, w] and neither y nor a.  A peak outside the grid or the classes seeds nothing.  P C h w < 2^31.
+ * cim_prmb_stem: the data gradient of the 7 x 7 / stride 2 / padding 3 stem convolution with wpos = max(W, 0) [cout][3][7][7],
+ *   fused with the multiply by xs [3][H][W], the sum over the 3 input channels and the clamp at 0:
+ *     out [P][H][W] = max(0, sum_ci xs[ci][y][x] sum_{co,ky,kx} ghat[p][co][(y + 3 - ky) / 2][(x + 3 - kx) / 2] wpos[co][ci][ky][kx])
+ *   over the taps with y + 3 - ky and x + 3 - kx even and inside ghat [P][cout][Ho][Wo], Ho = (H - 1) / 2 + 1.  normalise != 0: a
+ *   second launch divides every map by its sum (per-workgroup partial sums in double, added in a fixed order; a zero sum gives
+ *   NaN = 0 / 0 as the reference's prm / prm.sum()).  workspace: cim_prmb_stem_workspace(P, H, W) bytes, 8-byte aligned.
+ *   cout <= 256, P <= 65535, W <= 4096, H W < 2^22, any H and W. */
+#define CIM_PRMB_MIN_MAX_PARTS 1024
+long long cim_prmb_min_parts(long long n);
+int cim_prmb_min(const float* x, long long n, float* out, float* part, void* stream);
+int cim_prmb_shift(const float* x, const float* o, float* xs, long long n, void* stream);
+int cim_prmb_gate(const float* g, const float* mul, const float* y, const float* a, const float* n, float* dconv, float* dres,
+                  int P, int C, long long HW, void* stream);
+int cim_prmb_scale(const float* xs, const float* dxraw, const float* add, float* dx, int P, long long n, void* stream);
+int cim_prmb_seed(const int32_t* peaks_dev, const float* n, float* dconv, int P, int C, int h, int w, int factor, void* stream);
+long long cim_prmb_stem_workspace(int P, int H, int W);
+int cim_prmb_stem(const float* ghat, const float* wpos, const float* xs, float* out, void* workspace, int P, int cout, int H, int W,
+                  int normalise, void* stream);
+
 /* ------------------------------------------------------------------ Pillow's antialiased resize: raw RGB images to PRM inputs (ABI-16 addition)
  * Replaces the host call Image.resize((448, 448), Image.BILINEAR) in front of the PRM (tools/pre/AGPL_label_assign.py through
  * prm_configs.open_transform: transforms.Resize([448, 448]), ToTensor, Normalize) for a BATCH of images of differing sizes.
